@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the BA hot path on MI355X: BA iterations/sec on the 500-pose / 50 000-observation window.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" is one call of BA() (reference estimation/BA/BA_filtering.py:4-98) through the C ABI with every
 input already resident in HBM.  The steps walk the reference driver's own schedule (od_pipe.py:1036-1040):
@@ -18,12 +18,16 @@ host, so the replica measurement needs no RCCL and can be rehearsed with --gpus 
 LOCAL_RANK % device_count).  Every rank runs its own 500/50k window (the reference's outer loop over sequences,
 od_pipe.py:1063-1086): weak scaling, no data-path collective, value = N windows' iterations / max-over-ranks time.
 The observation-sharded mode (rows of ONE window split over the ranks, three all-gathers per call over RCCL) is
-measured in the same run on a separate nccl group and reported under "sharded" with the number of ranks RCCL saw; it
-is skipped, and says so, when two ranks share a device.
+measured in the same run with --full on a separate nccl group and reported under "sharded" with the number of ranks RCCL
+saw; it is skipped, and says so, when two ranks share a device.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant kernel class of the timed run, HIP-event
-timings on the library's stream; "whole_call" = SURVEY's algorithmic bytes of a call / ms_per_step; "mfma" =
-matrix-core counters of the solve kernels from the committed PMC pass), "cpu_baseline" (the NumPy oracle on ALL host
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the headline figure: metric, value,
+unit, higher_is_better, dtype, ms_per_step and the run's configuration.  --dump-outputs DIR then writes what the timed path
+computed in its last step (rank 0's window: the states and what vba_get_states returns with them) as DIR/<name>.npy in
+float64; the inputs are seeded, so the same arguments give the same inputs on every run.  Everything else is measured only
+with --full (the sharded leg included), on the same line.  Extra objects of --full: "roofline" (dominant kernel class of
+the timed run, HIP-event timings on the library's stream; "whole_call" = SURVEY's algorithmic bytes of a call /
+ms_per_step; "mfma" = matrix-core counters of the solve kernels from the committed PMC pass), "cpu_baseline" (the NumPy oracle on ALL host
 cores of this box, one single-threaded worker process per core over independent windows, bounded sample),
 "python_BA_call" (the drop-in vinsat_amd.ba.BA in the reference's loop shape), "host_roundtrip" (vba_iterate),
 "batched" (4096 windows per launch: the HBM-bound regime), "batched_sweep" (W = 1 .. 4096 windows per handle, kernel set and
@@ -89,6 +93,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="C3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as "
+                    "DIR/<name>.npy (float64, rank 0)")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline figure as well: CPU baseline, "
+                    "roofline and class times, the other call paths, windows per handle, configs, driver, accuracy against the "
+                    "reference's fixture, Schur add-on, sharded leg (the options below apply to these)")
     ap.add_argument("--windows", type=int, default=4096, help="windows per launch of the batched series (0 = skip)")
     ap.add_argument("--batched-steps", type=int, default=40)
     ap.add_argument("--sweep", default="1,2,4,8,15,16,22,32,64,128,256,1024", help="window counts of the batched_sweep series (the "
@@ -107,7 +116,10 @@ def parse():
     ap.add_argument("--dry-run", action="store_true", help="launcher / control-plane self-test without a GPU: ranks rendezvous "
                     "over gloo, take the barrier and the max-reduce, rank 0 prints a line marked dry_run (not a measurement)")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)    # self-test: this rank exits 7
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def schedule(k):
@@ -126,6 +138,20 @@ def run_steps(eng, st0, nsteps, windows=1):
         calls = [schedule(j) for j in range(cnt)]
         eng.run_schedule([c[0] for c in calls], [c[1] for c in calls])
         k += cnt
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float64, at most DUMP_LIMIT_BYTES in all."""
+    out = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"outputs of {total} bytes exceed the dump limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
 
 
 def load_windows(eng, win, n, W):
@@ -531,7 +557,7 @@ def run_rank(args):
 
     # CPU baseline first: its worker processes are started (and gone) before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and not args.dry_run:      # (N = 1 only: at N > 1 the other ranks would wait for it)
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and not args.dry_run:      # (N = 1 only: at N > 1 the other ranks would wait for it)
         try:
             cpu = cpu_baseline(args)
         except Exception as exc:
@@ -545,7 +571,7 @@ def run_rank(args):
         raise SystemExit("bench.py: no GPU visible (there is no CPU fallback)")
     device = local % ndev
     # VBA_BENCH_FORCE_DIST=1 takes the multi-rank code path (process groups, collectives, sharded window) even with a
-    # single rank -- the way to rehearse the RCCL leg on a one-GPU box
+    # single rank -- with --full, the way to rehearse the RCCL leg on a one-GPU box
     force_dist = os.environ.get("VBA_BENCH_FORCE_DIST") == "1"
     dist = None
     if world > 1 or force_dist:
@@ -593,6 +619,29 @@ def run_rank(args):
     # the MAX over ranks follow outside the region (timed_region)
     dt = timed_region(lambda: run_steps(eng, st0, args.steps), barrier, torch.cuda.synchronize, reduce_max)
     value = world * args.steps / dt
+    ms_per_step = 1e3 * dt / args.steps
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step: vba_get_states of the window
+        s_last, lam_last, hess_last, ntr_last, flags_last = eng.get_states()
+        dump_outputs(args.dump_outputs, {"states": s_last, "lamda": [lam_last], "last_hessian": hess_last,
+                                         "n_trials": [ntr_last], "flags": [flags_last]})
+    headline = {
+        "metric": METRIC,
+        "value": value, "unit": "BA iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"{cfg.name}: {n}-pose / {m}-observation window, 20-call schedule (10 landmark-only + 10 full)"
+                               + (f", {world} independent windows (one per rank)" if world > 1 else ""),
+                   "poses": n, "observations": m, "windows_per_gpu": 1, "parallelism": f"replicas{world}",
+                   "devices_visible": ndev, "ranks_per_device": (world + ndev - 1) // ndev},
+    }
+    if not args.full:
+        em.payload = headline
+        em.emit()
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # companion of the driver-sized sample (20 steps = 1 ms): the same loop over 200 steps, same bracketing
     dt200 = timed_region(lambda: run_steps(eng, st0, 200), barrier, torch.cuda.synchronize, reduce_max)
 
@@ -646,7 +695,6 @@ def run_rank(args):
             mfma["peak_TFLOPs"] = MFMA_F64_PEAK_TFLOPS
         except Exception:
             mfma = None
-    ms_per_step = 1e3 * dt / args.steps
     whole = survey_bytes_per_call(n, m)
     roofline = {"kernel": "solve class (chunk elimination + cyclic reduction of the separators + recovery)" if dom == "solve" else "k_" + dom,
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -912,15 +960,8 @@ def run_rank(args):
             schur = {"error": repr(exc)[:300]} if schur is None else dict(schur, large_error=repr(exc)[:300])
 
     em.payload = {
-        "metric": METRIC,
-        "value": value, "unit": "BA iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        **headline,
         "value_200": world * 200 / dt200, "ms_per_step_200": 1e3 * dt200 / 200,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"{cfg.name}: {n}-pose / {m}-observation window, 20-call schedule (10 landmark-only + 10 full)"
-                               + (f", {world} independent windows (one per rank)" if world > 1 else ""),
-                   "poses": n, "observations": m, "windows_per_gpu": 1, "parallelism": f"replicas{world}",
-                   "devices_visible": ndev, "ranks_per_device": (world + ndev - 1) // ndev},
         "phase_ms": {k: float(np.median(v)) if v else None for k, v in phase.items()},
         "phase_ms_source": "ten chained calls of the phase (vba_run_schedule), wall clock; their mean is ms_per_step plus one host synchronisation per ten calls",
         "chain_classes_ms": classes_ms,

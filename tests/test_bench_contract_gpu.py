@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "20",
-                          "--windows", "8", "--batched-steps", "20", "--cpu-seconds", "1"],
+                          "--full", "--windows", "8", "--batched-steps", "20", "--cpu-seconds", "1"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -41,7 +41,7 @@ def test_gpus_2_runs_two_replica_ranks_on_this_box():
     """The driver's `python bench.py --gpus N` must measure N ranks.  On a one-GPU box both ranks share the device (the
     control plane is gloo, replicas need no RCCL); the RCCL leg says that it was skipped."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "20",
-                          "--windows", "0", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--full", "--windows", "0", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -66,7 +66,7 @@ def test_gpus_2_rehearses_the_library_issued_sharded_leg_on_the_test_double_of_r
     subprocess.check_call(["make", "-C", fake_dir], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     env = dict(os.environ, VBA_BENCH_FAKE_RCCL="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "20", "--windows", "0",
-                          "--cpu-seconds", "0", "--sweep", "", "--no-configs", "--no-schur"], capture_output=True, text=True, timeout=900,
+                          "--full", "--cpu-seconds", "0", "--sweep", "", "--no-configs", "--no-schur"], capture_output=True, text=True, timeout=900,
                          cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
@@ -79,3 +79,32 @@ def test_gpus_2_rehearses_the_library_issued_sharded_leg_on_the_test_double_of_r
         assert e["poses"] == poses and e["observations_total"] == rows and e["observations_per_rank"] == rows // 2, (key, e)
         assert e["value_library_issued"] > 10 and e["one_gpu_unsharded"] > 10 and "native_error" not in e, (key, e)
         assert e["first_exchange_bytes_per_rank"] <= 32 * 1024 and e["calls_repeated_after_a_missed_select"] >= 0, (key, e)
+
+
+def test_a_plain_run_times_the_steps_and_dumps_what_the_last_timed_step_computed(tmp_path):
+    """Without --full the line holds the headline figure only.  --steps sets the timed steps (20 = one whole schedule, 30 = a
+    schedule and ten calls of the next), and --dump-outputs writes what the last of them computed: against the reference's
+    states after that call of its own run on the same inputs (tests/golden/c3.npz)."""
+    import numpy as np
+    from conftest import load_golden, rel_err
+    g = load_golden("c3")
+    for steps, last in ((20, 19), (30, 9)):
+        dump = tmp_path / f"steps{steps}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "5",
+                              "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == steps and d["warmup"] == 5 and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert d["value"] > 100 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+        for key in ("value_200", "roofline", "cpu_baseline", "accuracy", "batched", "configs", "driver", "schur_addon"):
+            assert key not in d, key
+        res = {name: np.load(dump / f"{name}.npy") for name in ("states", "lamda", "last_hessian", "n_trials", "flags")}
+        assert all(a.dtype == np.float64 for a in res.values())
+        assert res["states"].shape == (500, 10) and res["last_hessian"].shape == (9, 9)
+        st, ref = res["states"], g[f"states_out_{last}"][0]
+        assert np.abs(st[:, :3] - ref[:, :3]).max() / np.abs(ref[:, :3]).max() < 1e-6 and rel_err(st, ref) < 1e-6, last
+        assert res["lamda"][0] == g["lamda_out"][last] and res["n_trials"][0] == g["n_trials"][last] and res["flags"][0] == 0

@@ -77,3 +77,18 @@ def test_cpu_baseline_worker_protocol():
     p.stdin.close()
     assert p.wait(timeout=60) == 0
     assert res["calls"] >= 20 and res["calls"] % 20 == 0 and res["seconds"] > 0
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_size_limit(tmp_path):
+    # --dump-outputs: DIR/<name>.npy in float64 whatever the dtype handed in; more than 64 MB in all is refused, nothing written
+    import numpy as np
+    import pytest
+    sys.path.insert(0, ROOT)
+    import bench
+    bench.dump_outputs(str(tmp_path / "out"), {"states": np.arange(20.0).reshape(2, 10), "n_trials": [3], "flags": np.uint32([5])})
+    got = {name: np.load(tmp_path / "out" / f"{name}.npy") for name in ("states", "n_trials", "flags")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["states"], np.arange(20.0).reshape(2, 10)) and got["n_trials"][0] == 3 and got["flags"][0] == 5
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1, dtype=np.float32)})
+    assert not (tmp_path / "big").exists()
