@@ -166,9 +166,25 @@ enum {
     VBA_OPT_SCHEDULE_GRAPH = 11,    /* 1 (default, latency mode): vba_run_schedule replays the launches of its first pass as a hipGraph while
                                        nothing that goes into them has changed (per-call kernel arguments compared exactly); a capture that
                                        fails switches it off for the handle and the pass is launched kernel by kernel; also VBA_NO_GRAPH */
-    VBA_OPT_CHAIN_PROFILE = 12      /* 1: vba_run_schedule records HIP events at the class boundaries of every call (~1 us each, no graph
+    VBA_OPT_CHAIN_PROFILE = 12,     /* 1: vba_run_schedule records HIP events at the class boundaries of every call (~1 us each, no graph
                                        replay meanwhile): vba_chain_profile */
+    VBA_OPT_JACOBIAN_F32 = 13       /* 0 (default): fp64 throughout.  1: the terms of the reprojection Jacobian in fp32 (contract below)
+                                       -- the one option that changes results beyond the last bits */
 };
+/* VBA_OPT_JACOBIAN_F32 = 1, the precision contract.  Only the observation accumulation changes:
+ *   fp32: the camera-frame point p_c and d = 1/z rounded to fp32; the camera-frame Jacobian terms -- A = d uv / d p_c (four
+ *         non-zeros) and Gr = 2 A hat(p_c) -- evaluated in fp32 (cam_jacobian_f32, vba_math.h).
+ *   fp64, unchanged: projection, residual, robust weights, the exact median and c_obs; the weighted products and the per-lane
+ *         sums of BOTH parts, H (w A^T A, w A^T Gr, w Gr^T Gr) and b (w A^T r, w Gr^T r), formed from the fp32 terms widened;
+ *         the cross-lane reduction, the rotation to the world frame and the assembly; the dynamics, attitude and long-gap
+ *         factors; trial residuals, the LM test, the solve.
+ *   The H sums are kept in fp64 because a measurement decided it: a pose's 6x6 block is nearly singular along "translate across
+ *   the line of sight = rotate" (condition ~1e10 in the landmark-only calls), and fp32 sums moved the first call's states of
+ *   the C3 window by 5e-4 (position, relative) and 2e-3 rad against the reference.
+ *   Every accumulation shape (VBA_OPT_ACCUMULATE_LANES 4 .. 64, either kernel set) uses the camera-frame form in this mode, so
+ *   shapes differ only in summation order.  vba_debug_fetch(VBA_DBG_JG) returns the fp32 terms rotated in fp64 -- the Jacobian
+ *   the sums were formed from.  A schedule graph or a speculated call of one mode is never replayed in the other.  It does not
+ *   pay on the MI355X; it exists because BASELINE config 5 names it. */
 int vba_set_option(vba_handle h, int option, int value);
 
 /* BA_reg (BA_filtering.py:100-210): the BA call with a propagated-covariance prior per pose.

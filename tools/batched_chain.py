@@ -25,6 +25,9 @@ for w in range(W):
     e.upload_window(win.intrinsics, win.cumrot_last, win.time_idx, window=w)
 if os.environ.get("VBA_FUSION"):
     e.set_fusion(int(os.environ["VBA_FUSION"]))
+if os.environ.get("VBA_JACOBIAN", "fp64") not in ("fp64", "fp32"):
+    sys.exit("VBA_JACOBIAN must be fp64 or fp32")
+e.set_jacobian_f32(os.environ.get("VBA_JACOBIAN") == "fp32")     # VBA_JACOBIAN=fp32: VBA_OPT_JACOBIAN_F32
 iters, inits = list(range(20)), [k < 10 for k in range(20)]
 e.set_states(st0, 1e-4, window=-1)
 e.run_schedule(iters, inits)

@@ -86,7 +86,7 @@ SIGNATURES = {
 
 # VBA_OPT_* of include/vinsat_ba.h (vba_set_option)
 OPT = dict(accumulate_lanes=1, trial_tiles=2, key_carry=3, warm_select=4, warm_shift=5, bucket_cap=6, fusion=7, chunk_waves=8,
-           pivoting=9, pipeline=10, schedule_graph=11, chain_profile=12)
+           pivoting=9, pipeline=10, schedule_graph=11, chain_profile=12, jacobian_f32=13)
 
 _lib = None
 

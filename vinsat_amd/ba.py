@@ -131,13 +131,17 @@ def _numpy_unchanged(args):
     return True
 
 
-def configure(integrator=None, lanes=None, fusion=None, solver=None, mode=None, strict=None):
+def configure(integrator=None, lanes=None, fusion=None, solver=None, mode=None, strict=None, jacobian=None):
     """Settings of the cached engines that the reference's call surface has no argument for.
 
     ``integrator``: ``"rk4"`` (default) = one-second RK4 steps, the reference's CPU branch ``predict``
     (``BA_utils.py:73-87``) -- the parity target; ``"hop"`` = the <=100 s hops of ``predict_gpu``
     (``BA_utils.py:52-71, 529-602``), which is what the reference itself runs when it sees a GPU
     (``BA_filtering.py:16-17``).  Takes effect from the next call on.
+
+    ``jacobian``: ``"fp64"`` (default) or ``"fp32"`` = the terms of the reprojection Jacobian in fp32, everything else in
+    fp64 (``VBA_OPT_JACOBIAN_F32``; ``include/vinsat_ba.h`` states the contract).
+    Takes effect from the next call on.
 
     ``lanes`` / ``fusion`` / ``solver`` / ``mode`` pin what a handle otherwise chooses from its own geometry -- lanes per
     pose of the accumulation (``VBA_OPT_ACCUMULATE_LANES``: the shape of its reduction tree), the kernel-fusion mask
@@ -161,6 +165,16 @@ def configure(integrator=None, lanes=None, fusion=None, solver=None, mode=None, 
                 eng.set_integrator(_cache["hop"])
         _cache["resident"] = None
         _cache["bresident"] = None
+    if jacobian is not None:
+        if jacobian not in ("fp64", "fp32"):
+            raise ValueError("jacobian must be 'fp64' or 'fp32'")
+        _cache["jac_f32"] = jacobian == "fp32"
+        for key in ("eng", "beng"):
+            eng = _cache.get(key)
+            if eng is not None:
+                eng.set_jacobian_f32(_cache["jac_f32"])
+        _cache["resident"] = None
+        _cache["bresident"] = None
     pins = dict(_cache.get("pins", {}))
     changed = False
     for name, val in (("lanes", lanes), ("fusion", fusion), ("solver", solver), ("mode", mode)):
@@ -181,6 +195,8 @@ def _new_engine(n_max, m_max, windows, device):
     pins = _cache.get("pins", {})
     eng = BAEngine(n_max, m_max, windows=windows, device=device, mode={"lat": 1, "bw": 0}.get(pins.get("mode"), pins.get("mode", -1)))
     eng.set_integrator(bool(_cache.get("hop", False)))
+    if _cache.get("jac_f32"):
+        eng.set_jacobian_f32(True)
     if "lanes" in pins:
         eng.set_accumulate_lanes(pins["lanes"])
     if "fusion" in pins:

@@ -107,7 +107,7 @@ static int vba_set_accumulate_lanes(vba_handle h, int lanes);
 static int vba_set_trial_tiles(vba_handle h, int tiles);
 int vba_set_solver(vba_handle h, int chunk);
 
-int vba_version(void) { return 210; }     // 2.1: vba_set_chunk_waves, fusion bits 2..4, warm select mode 3
+int vba_version(void) { return 220; }     // 2.2: VBA_OPT_JACOBIAN_F32 (2.1: vba_set_chunk_waves, fusion bits 2..4, warm select mode 3)
 
 const char* vba_last_error(void) { return g_err.c_str(); }
 
@@ -606,6 +606,16 @@ int vba_warm_select_misses(vba_handle h, int* count) {
     return VBA_OK;
 }
 
+// fp32 reprojection Jacobian (include/vinsat_ba.h: what is fp32).  A flag of the view: the schedule graphs of the two modes are
+// told apart by their view bytes, and the settle drops a call speculated in the other mode.
+static int vba_set_jacobian_f32(vba_handle h, int on) {
+    if (!h) return fail(VBA_EINVAL, "null handle");
+    if (int rc_settle = settle(h)) return rc_settle;
+    if (on != 0 && on != 1) return fail(VBA_EINVAL, "jacobian_f32 must be 0 (fp64, default) or 1 (fp32)");
+    h->V.jac_f32 = on;
+    return VBA_OK;
+}
+
 static int vba_set_pivoting(vba_handle h, int always) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
@@ -894,6 +904,7 @@ int vba_set_option(vba_handle h, int option, int value) {
         case VBA_OPT_PIPELINE: return vba_set_pipeline(h, value);
         case VBA_OPT_SCHEDULE_GRAPH: return vba_set_schedule_graph(h, value);
         case VBA_OPT_CHAIN_PROFILE: return vba_set_chain_profile(h, value);
+        case VBA_OPT_JACOBIAN_F32: return vba_set_jacobian_f32(h, value);
         default: return fail(VBA_EINVAL, "unknown option (VBA_OPT_*)");
     }
 }

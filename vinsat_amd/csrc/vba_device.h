@@ -177,6 +177,7 @@ struct DevView {
     double* wraw;                   // [W][m_max]    raw robust weight
     double* ckeys;                  // [W][2 m_max]  keys surviving the first two select digits (usually a handful)
     int acc_lanes;                  // lanes per pose in k_obs_accumulate (4..64)
+    int jac_f32;                    // k_obs_accumulate: fp32 Jacobian terms and H sums (VBA_OPT_JACOBIAN_F32; a graph key like every field)
     double* part_init;              // [W][nblk_obs] block sums of |r_obs|
     double* part_trial;             // [W][trial_stride]: nblk_obs observation blocks, then nblk_dyn pose-chain blocks, then nblk_long long edges
     double* part_next;              // [W][nblk_obs] block sums of |r_obs| at the trial states (carried keys)

@@ -1,4 +1,4 @@
-// vba_math.h -- per-observation / per-pose arithmetic of the BA iteration, fp64.
+// vba_math.h -- per-observation / per-pose arithmetic of the BA iteration, fp64 (the opt-in fp32 Jacobian aside).
 //
 // Pure functions shared by the HIP kernels.  They compile for the host as well (plain C++), which the
 // test-suite uses to check the formulas on a machine without a GPU; the product never runs them there.
@@ -110,6 +110,37 @@ VBA_HD void project_jacobian(const PoseCam& pc, const double* cam, double d, dou
     J[9] = 2.0 * (a11 * z - a12 * y);
     J[10] = 2.0 * (a12 * x);
     J[11] = 2.0 * (-a11 * x);
+}
+
+// fp32 Jacobian (VBA_OPT_JACOBIAN_F32, include/vinsat_ba.h states the contract): the camera-frame terms of project_jacobian
+// -- A = d uv / d p_c (a00, a02, a11, a12; a01 = a10 = 0) and Gr = 2 A hat(p_c) (rows g, h) -- from the camera-frame point
+// and d = 1/z rounded to fp32, every operation in fp32, in the order k_obs_accumulate's camera-frame form evaluates them.
+struct CamJac32 { float a00, a02, a11, a12, g0, g1, g2, h0, h1, h2; };
+VBA_HD CamJac32 cam_jacobian_f32(const PoseCam& pc, const double* cam, double d) {
+    const float x = (float)cam[0], y = (float)cam[1], z = (float)cam[2], df = (float)d;
+    const float dl = cam[2] > kZMin ? df : 0.0f;
+    CamJac32 j;
+    j.a00 = (float)pc.fx * df;
+    j.a11 = (float)pc.fy * df;
+    j.a02 = -(j.a00 * (x * dl));
+    j.a12 = -(j.a11 * (y * dl));
+    const float b00 = 2.0f * j.a00, b02 = 2.0f * j.a02, b11 = 2.0f * j.a11, b12 = 2.0f * j.a12;
+    j.g0 = -(b02 * y); j.g1 = fmaf(b02, x, -(b00 * z)); j.g2 = b00 * y;
+    j.h0 = fmaf(b11, z, -(b12 * y)); j.h1 = b12 * x; j.h2 = -(b11 * x);
+    return j;
+}
+
+// The world-frame 2x6 Jacobian of the fp32 terms, [-A R^T | Gr] with the rotation in fp64: what the accumulation's sums are
+// sums of in fp32 mode (k_debug_project returns it).  J row major [2][6].
+VBA_HD void project_jacobian_f32(const PoseCam& pc, const double* cam, double d, double* J) {
+    const CamJac32 j = cam_jacobian_f32(pc, cam, d);
+    const double a00 = j.a00, a02 = j.a02, a11 = j.a11, a12 = j.a12;
+    for (int c = 0; c < 3; ++c) {
+        J[c] = -(a00 * pc.R[3 * c + 0] + a02 * pc.R[3 * c + 2]);
+        J[6 + c] = -(a11 * pc.R[3 * c + 1] + a12 * pc.R[3 * c + 2]);
+    }
+    J[3] = j.g0; J[4] = j.g1; J[5] = j.g2;
+    J[9] = j.h0; J[10] = j.h1; J[11] = j.h2;
 }
 
 // ------------------------------------------------------------------------------------------------ weights

@@ -643,7 +643,9 @@ __device__ __forceinline__ void halving_steps(double (&acc)[32], int sub, int& o
     }
 }
 
-template <int G, bool PAIR, bool BATCH>
+// F32 (VBA_OPT_JACOBIAN_F32): the camera-frame Jacobian terms in fp32 (cam_jacobian_f32), their products and sums in fp64;
+// every G takes the camera-frame form then (include/vinsat_ba.h: the precision contract).
+template <int G, bool PAIR, bool BATCH, bool F32 = false>
 __global__ __launch_bounds__(256) void k_obs_accumulate(DevView V) {
     __shared__ double wmx[4];
     __shared__ unsigned sel_lh[BATCH ? 1 : kSelBins];
@@ -852,7 +854,7 @@ __global__ __launch_bounds__(256) void k_obs_accumulate(DevView V) {
     // G_k = [ -A | 2 A hat(p_c) ], whose translation part is the sparse A itself -- and rotates its sums once at the end
     // (J^T J = T G^T G T^T, T = diag(R, I)): ~130 VALU instructions per row instead of ~215.  Few rows per lane (latency
     // mode, 32 / 64 lanes per pose): the rotation per lane would cost what it saves, J is formed per row.
-    constexpr bool CAM = G <= 16;
+    constexpr bool CAM = G <= 16 || F32;
     double acc[32];         // 21 + 6 sums, padded to a power of two for the halving reduction
 #pragma unroll
     for (int q = 0; q < 32; ++q) acc[q] = 0.0;
@@ -868,16 +870,9 @@ __global__ __launch_bounds__(256) void k_obs_accumulate(DevView V) {
             V.wraw[mb + k] = wr;
             wmax_l = fmax(wmax_l, wr);
             const double wc = wr * oc_;
-            if (CAM) {
-                const double live = cam[2] > kZMin ? 1.0 : 0.0;
-                const double a00 = pc.fx * d, a11 = pc.fy * d;
-                const double dl = d * live;
-                const double a02 = -(a00 * (cam[0] * dl)), a12 = -(a11 * (cam[1] * dl));
-                const double x = cam[0], y = cam[1], z = cam[2];
-                // Gr = 2 A hat(p_c): rows (g0..g2) and (h0..h2)
-                const double b00 = 2.0 * a00, b02 = 2.0 * a02, b11 = 2.0 * a11, b12 = 2.0 * a12;
-                const double g0 = -(b02 * y), g1 = fma(b02, x, -(b00 * z)), g2 = b00 * y;
-                const double h0 = fma(b11, z, -(b12 * y)), h1 = b12 * x, h2 = -(b11 * x);
+            // the camera-frame sums of one row (CAM): terms of A and Gr = 2 A hat(p_c), rows (g0..g2) and (h0..h2)
+            auto cam_sums = [&](double a00, double a02, double a11, double a12, double g0, double g1, double g2, double h0, double h1,
+                                double h2) {
                 const double w00 = wc * a00, w02 = wc * a02, w11 = wc * a11, w12 = wc * a12;
                 cM[0] = fma(w00, a00, cM[0]); cM[1] = fma(w00, a02, cM[1]);
                 cM[2] = fma(w11, a11, cM[2]); cM[3] = fma(w11, a12, cM[3]);
@@ -894,6 +889,20 @@ __global__ __launch_bounds__(256) void k_obs_accumulate(DevView V) {
                 cS[0] = fma(w00, ru, cS[0]); cS[1] = fma(w11, rv, cS[1]); cS[2] = fma(w02, ru, fma(w12, rv, cS[2]));
                 acc[24] = fma(wg0, ru, fma(wh0, rv, acc[24])); acc[25] = fma(wg1, ru, fma(wh1, rv, acc[25]));
                 acc[26] = fma(wg2, ru, fma(wh2, rv, acc[26]));
+            };
+            if constexpr (F32) {        // the fp32 terms, widened: products and sums in fp64
+                const CamJac32 j = cam_jacobian_f32(pc, cam, d);
+                cam_sums(j.a00, j.a02, j.a11, j.a12, j.g0, j.g1, j.g2, j.h0, j.h1, j.h2);
+            } else if (CAM) {
+                const double live = cam[2] > kZMin ? 1.0 : 0.0;
+                const double a00 = pc.fx * d, a11 = pc.fy * d;
+                const double dl = d * live;
+                const double a02 = -(a00 * (cam[0] * dl)), a12 = -(a11 * (cam[1] * dl));
+                const double x = cam[0], y = cam[1], z = cam[2];
+                const double b00 = 2.0 * a00, b02 = 2.0 * a02, b11 = 2.0 * a11, b12 = 2.0 * a12;
+                const double g0 = -(b02 * y), g1 = fma(b02, x, -(b00 * z)), g2 = b00 * y;
+                const double h0 = fma(b11, z, -(b12 * y)), h1 = b12 * x, h2 = -(b11 * x);
+                cam_sums(a00, a02, a11, a12, g0, g1, g2, h0, h1, h2);
             } else {
                 double J[12];
                 project_jacobian(pc, cam, d, J);
@@ -1458,7 +1467,8 @@ __global__ __launch_bounds__(kObsBlock) void k_debug_project(DevView V, int w, d
     project(pc, V.ox[ob + k], V.oy[ob + k], V.oz[ob + k], u, v, cam, d);
     est[2 * k] = u;
     est[2 * k + 1] = v;
-    project_jacobian(pc, cam, d, J + 12 * (size_t)k);
+    if (V.jac_f32) project_jacobian_f32(pc, cam, d, J + 12 * (size_t)k);      // the Jacobian the fp32 accumulation used
+    else project_jacobian(pc, cam, d, J + 12 * (size_t)k);
     wt[k] = (V.wraw[mb + k] / bits_f64(V.sc[w].wmax_bits[V.par])) * V.oconf[ob + k];
 }
 
@@ -1564,16 +1574,34 @@ void launch_select_finish(const DevView& V, hipStream_t s) {
     hipLaunchKernelGGL(k_select_finish, dim3(V.W), dim3(256), 0, s, V);
 }
 
+#ifndef VBA_ACC_PAIR
+#define VBA_ACC_PAIR 1
+#endif
+constexpr bool kPair = VBA_ACC_PAIR != 0;
+
+template <bool F32>
+static void launch_acc_batch(int G, dim3 g, dim3 b, hipStream_t s, const DevView& V) {
+    if (G == 8) hipLaunchKernelGGL((k_obs_accumulate<8, kPair, true, F32>), g, b, 0, s, V);
+    else hipLaunchKernelGGL((k_obs_accumulate<16, false, true, F32>), g, b, 0, s, V);
+}
+
+template <bool F32>
+static void launch_acc_lanes(int G, dim3 g, dim3 b, hipStream_t s, const DevView& V) {
+    switch (G) {
+        case 4: hipLaunchKernelGGL((k_obs_accumulate<4, kPair, false, F32>), g, b, 0, s, V); break;
+        case 8: hipLaunchKernelGGL((k_obs_accumulate<8, kPair, false, F32>), g, b, 0, s, V); break;
+        case 16: hipLaunchKernelGGL((k_obs_accumulate<16, false, false, F32>), g, b, 0, s, V); break;
+        case 32: hipLaunchKernelGGL((k_obs_accumulate<32, false, false, F32>), g, b, 0, s, V); break;
+        default: hipLaunchKernelGGL((k_obs_accumulate<64, false, false, F32>), g, b, 0, s, V); break;
+    }
+}
+
 void launch_obs_accumulate(const DevView& V, hipStream_t s) {
     const int G = V.acc_lanes;
     const int nb = (V.n_max * G + 255) / 256;
     // V.dyn_in_acc: the blocks of the dynamics factor are appended to the grid
     // V.sel_inline: one more block, which evaluates the folded accept test and records the start of the call
     const dim3 g(nb + (V.dyn_in_acc ? (V.n_max * kDynLanes + 255) / 256 : 0) + (V.sel_inline ? 1 : 0), V.W), b(256);
-#ifndef VBA_ACC_PAIR
-#define VBA_ACC_PAIR 1
-#endif
-    constexpr bool kPair = VBA_ACC_PAIR != 0;
     if (V.median_ready && !V.dyn_in_acc && !V.sel_inline && (G == 8 || G == 16)) {      // many windows per launch
 #ifndef VBA_ACC_GROUPS
 #define VBA_ACC_GROUPS 4
@@ -1585,17 +1613,12 @@ void launch_obs_accumulate(const DevView& V, hipStream_t s) {
         while (groups > 1 && (int64_t)V.W * ((nb + groups - 1) / groups) < 2048) groups >>= 1;
         if (groups_env > 0) groups = groups_env;
         const dim3 gb((nb + groups - 1) / groups, V.W);
-        if (G == 8) hipLaunchKernelGGL((k_obs_accumulate<8, kPair, true>), gb, b, 0, s, V);
-        else hipLaunchKernelGGL((k_obs_accumulate<16, false, true>), gb, b, 0, s, V);
+        if (V.jac_f32) launch_acc_batch<true>(G, gb, b, s, V);
+        else launch_acc_batch<false>(G, gb, b, s, V);
         return;
     }
-    switch (G) {
-        case 4: hipLaunchKernelGGL((k_obs_accumulate<4, kPair, false>), g, b, 0, s, V); break;
-        case 8: hipLaunchKernelGGL((k_obs_accumulate<8, kPair, false>), g, b, 0, s, V); break;
-        case 16: hipLaunchKernelGGL((k_obs_accumulate<16, false, false>), g, b, 0, s, V); break;
-        case 32: hipLaunchKernelGGL((k_obs_accumulate<32, false, false>), g, b, 0, s, V); break;
-        default: hipLaunchKernelGGL((k_obs_accumulate<64, false, false>), g, b, 0, s, V); break;
-    }
+    if (V.jac_f32) launch_acc_lanes<true>(G, g, b, s, V);
+    else launch_acc_lanes<false>(G, g, b, s, V);
     // the long edges of the dynamics factor that rode in this grid (behind the folded accept test: the window has moved on to
     // this call, or the kernel leaves it alone as every later kernel of the call does)
     if (V.dyn_in_acc) launch_long_factor(V, s);

@@ -196,12 +196,15 @@ class ShardedBA:
         self.n_trials = 0
 
     @classmethod
-    def from_window(cls, win, device=0, group=None, collectives=None, native=False, rccl_path=None):
+    def from_window(cls, win, device=0, group=None, collectives=None, native=False, rccl_path=None, jacobian="fp64"):
         """Build the GPU-backed sharded solver for a :class:`vinsat_amd.od_pipe.Window` on this rank.
 
         ``native``: the library issues the all-gathers itself (RCCL on its own stream, ``vba_sh_call``); ``group`` is then
         only the control plane over which the communicator's id is handed out (any backend); ``rccl_path`` names the library
-        that provides the collectives (default: the RCCL this process has loaded)."""
+        that provides the collectives (default: the RCCL this process has loaded).  ``jacobian``: ``"fp64"`` (default) or
+        ``"fp32"``, as :func:`vinsat_amd.ba.configure` -- every rank should pass the same."""
+        if jacobian not in ("fp64", "fp32"):
+            raise ValueError("jacobian must be 'fp64' or 'fp32'")
         import torch.distributed as dist
         from .engine import BAEngine
         if collectives is not None:
@@ -213,6 +216,7 @@ class ShardedBA:
         # every rank sizes its handle for ceil(m / world) rows: the exchange buffers of the library-issued protocol are laid out by
         # the handle's geometry (observation blocks, bucket capacity) and must be the same on all ranks
         eng = BAEngine(n, max(-(-m // world), 1), windows=1, device=device)
+        eng.set_jacobian_f32(jacobian == "fp32")
         eng.upload_observations(win.landmarks_xyz[lo:hi], win.landmarks_uv[lo:hi], win.confidences[lo:hi], win.ii[lo:hi], n)
         eng.upload_window(win.intrinsics, win.cumrot_last, win.time_idx)
         if native:

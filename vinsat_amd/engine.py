@@ -74,6 +74,11 @@ class BAEngine:
         """False: 1 s RK4 steps (reference CPU branch, default); True: <=100 s hops (the reference's predict_gpu)."""
         _lib.check(self.lib.vba_set_integrator(self.h, int(bool(hop100))), self.lib)
 
+    def set_jacobian_f32(self, on):
+        """True: the terms of the reprojection Jacobian in fp32, everything else in fp64 (``VBA_OPT_JACOBIAN_F32``;
+        ``include/vinsat_ba.h`` states what is fp32).  False (default): fp64 throughout."""
+        self._option("jacobian_f32", int(bool(on)))
+
     def set_accumulate_lanes(self, lanes):
         """Lanes per pose of the accumulation kernel (0 = automatic)."""
         self._option("accumulate_lanes", int(lanes))

@@ -197,7 +197,8 @@ def run_folder(folder, ba=None, batched=False, gpus=None, workers_per_gpu=1, con
     worker that owns the sequence, so ``workers_per_gpu`` > 1 also hides it behind another worker's kernels.  ``ba`` must then
     be None or a ``"module:attribute"`` string (it has to be importable in the workers).  ``configure``: keyword arguments of
     :func:`vinsat_amd.ba.configure` applied in every worker (pinned handle settings give a sequence the same bits whichever
-    worker and batch it lands in).  ``stats`` (a list) receives one dict per worker: device, sequences, rows, wall and phase times."""
+    worker and batch it lands in); ``configure={"jacobian": "fp32"}`` runs every worker in the fp32-Jacobian mode with no more
+    than that.  ``stats`` (a list) receives one dict per worker: device, sequences, rows, wall and phase times."""
     pairs = list(_pairs(folder))
     if gpus is None:
         if configure:
