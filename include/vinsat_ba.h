@@ -218,9 +218,16 @@ int vba_solver_fallbacks(vba_handle h, int* count);
 int vba_upload_observations(vba_handle h, int window, int n, int64_t m, const double* landmarks_xyz,
                             const double* landmarks_uv, const double* confidences, const int64_t* ii);
 
+/* The longest gap between two consecutive poses that vba_upload_window accepts, in seconds (2^20 s, ~12 days).  A gap is walked
+ * in one-second RK4 steps; a long one is cut into at most 64 chunks of L >= gap / 64 steps (csrc/vba_long.hip), and a gap the
+ * window's chain pool has no room for takes one lane's serial walk -- the limit keeps either within 2^20 steps of one lane.
+ * The reference's driver inserts a knot every 1000 s (od_pipe.py:213-221): its gaps never come near it. */
+enum { VBA_MAX_GAP = 1 << 20 };
+
 /* Per-pose constants of window `window`: intrinsics [n,4] = fx,fy,cx,cy; cumrot_last [n,4] =
  * imu_meas[0,:,-1,6:10], the attitude increment over the gap that follows each pose (the only part of
- * imu_meas the reference's CPU path reads, BA_utils.py:295); time_idx [n] seconds, strictly increasing. */
+ * imu_meas the reference's CPU path reads, BA_utils.py:295); time_idx [n] seconds, strictly increasing, no two consecutive
+ * ones more than VBA_MAX_GAP apart (VBA_EINVAL otherwise, before anything is uploaded). */
 int vba_upload_window(vba_handle h, int window, int n, const double* intrinsics, const double* cumrot_last,
                       const int64_t* time_idx);
 

@@ -1,6 +1,7 @@
 // Host build of vinsat_amd/csrc/vba_math.h for the CPU test-suite (formula checks without a GPU).
 // Test infrastructure only: nothing in the product loads this.
 #include "../../vinsat_amd/csrc/vba_math.h"
+#include "../../include/vinsat_ba.h"
 #include <cstdint>
 using namespace vba;
 
@@ -83,6 +84,18 @@ void hc_assemble(int n, const double* Hraw, const double* braw, double inv_wmax,
         for (int a = 0; a < 9; ++a) rhs[9 * i + a] = rhs_entry(R, a);
     }
 }
+
+// the plan of a long gap (vba_long.hip) for each of n step counts: L, P, sub, nsubL, G and the pool states the upload reserves
+void hc_long_plan(int64_t n, const int64_t* s, int64_t* out /*[n,6]*/) {
+    for (int64_t k = 0; k < n; ++k) {
+        const LongPlan p = long_plan((int)s[k]);
+        int64_t* o = out + 6 * k;
+        o[0] = p.L; o[1] = p.P; o[2] = p.sub; o[3] = p.nsubL; o[4] = p.G;
+        o[5] = long_pool_states(p);     // what vba_upload_window reserves
+    }
+}
+
+int hc_max_gap() { return VBA_MAX_GAP; }
 
 void hc_retract(int n, const double* states, const double* dpose, double* out) {
     for (int i = 0; i < n; ++i) retract(states + 10 * i, dpose + 9 * i, out + 10 * i);

@@ -92,6 +92,14 @@ int main() {
         for (int b = 0; b < 6; ++b)
             if (sym6(a, b) < 0 || sym6(a, b) > 20) return 2;
 
+    // the plan of a long gap up to the longest gap an upload accepts (signed overflow in it is what UBSan would report)
+    for (int s = 65; s <= VBA_MAX_GAP; s += s < 20000 ? 1 : 997) {
+        const LongPlan pl = long_plan(s);
+        if (pl.P > 64 || pl.G > 128 || (int64_t)(pl.P - 1) * pl.L >= s || (int64_t)pl.P * pl.L < s) return 4;
+    }
+    const LongPlan top = long_plan(VBA_MAX_GAP);
+    if (top.P > 64 || top.G > 128) return 4;
+
     double chk = acc;
     for (double v : est) chk += v;
     for (double v : out) chk += v;

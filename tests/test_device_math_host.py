@@ -162,3 +162,42 @@ def test_device_math_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "sanitize_main ok" in p.stdout and "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr
+
+
+# ------------------------------------------------------------------------------------------------ plan of a long gap
+def _long_plan_py(s):
+    """vba_math.h long_plan restated with Python integers (no overflow): (L, P, sub, nsubL, G)."""
+    L = 1
+    while 45 * L * L < 34 * s:
+        L += 1
+    if 64 * L < s:
+        L = (s + 63) // 64
+    P = (s + L - 1) // L
+    per_chunk = min(128 // P, 4)
+    sub = max((L + per_chunk - 1) // per_chunk, 8)
+    nsubL = (L + sub - 1) // sub
+    last = s - (P - 1) * L
+    return L, P, sub, nsubL, (P - 1) * nsubL + (last + sub - 1) // sub
+
+
+def test_long_plan_against_python_integers_up_to_the_gap_limit(hc):
+    """The plan of a long gap (vba_long.hip), the same function on the host (pool size) and on the device: every step count of
+    65 .. 20 000, then sampled up to VBA_MAX_GAP -- where 45 L^2 in 32-bit arithmetic would have overflowed above ~6.3e7 s.
+    P <= 64 chunks (a wavefront's lanes), (P - 1) L < s <= P L (the tail chunk is not empty), G <= 128 sub-chunks (kLongSplit
+    workgroups of 16), the sub-chunks of a chunk cover it, and the pool reserves header + G + 48 states."""
+    hc.hc_max_gap.restype = ctypes.c_int
+    gmax = hc.hc_max_gap()
+    assert gmax == 2 ** 20
+    rng = np.random.default_rng(0)
+    s = np.unique(np.concatenate([np.arange(65, 20001), rng.integers(20001, gmax, 3000), [gmax - 1, gmax]])).astype(np.int64)
+    out = np.zeros((s.size, 6), dtype=np.int64)
+    hc.hc_long_plan(ctypes.c_int64(s.size), _pi(s), _pi(out))
+    for k in range(s.size):
+        si = int(s[k])
+        L, P, sub, nsubL, G = out[k, :5]
+        assert tuple(int(v) for v in out[k, :5]) == _long_plan_py(si), si
+        assert 1 <= P <= 64 and (P - 1) * L < si <= P * L, si
+        assert 1 <= G <= 128 and nsubL * sub >= L and sub >= 8, si
+        assert out[k, 5] == 3 + G + 48, si
+    # the longest gap an upload accepts: 64 chunks of 16 384 steps
+    assert tuple(out[-1, :2]) == (2 ** 14, 64)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, rel_err
+from state_metrics import assert_states
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +48,7 @@ def _check_against_fixture(name, g, k, st, lam, ntr):
     assert np.abs(st[:, :3] - ref[:, :3]).max() / np.abs(ref[:, :3]).max() < 1e-6, (name, k)
     assert (2 * np.arccos(np.clip(np.abs((st[:, 3:7] * ref[:, 3:7]).sum(-1)), 0, 1))).max() < 1e-6, (name, k)
     assert rel_err(st, ref) < 1e-6, (name, k)
+    assert_states(st, ref, 1e-6, 1e-6, 1e-6, (name, k))
     assert lam == g["lamda_out"][k] and ntr == g["n_trials"][k], (name, k, lam, ntr)
 
 

@@ -18,6 +18,7 @@ import pytest
 
 from conftest import GOLDEN, load_golden, rel_err  # noqa: F401  (c2 fixture comes from conftest)
 from oracle import ba_oracle as O
+from state_metrics import assert_states
 
 pytestmark = pytest.mark.gpu
 
@@ -48,6 +49,7 @@ def _close_to_reference(st, ref, k):
     q, qr = st[:, 3:7], ref[:, 3:7]
     assert (2 * np.arccos(np.clip(np.abs((q * qr).sum(-1)), 0, 1))).max() < 1e-6, k
     assert rel_err(st, ref) < 1e-6, k
+    assert_states(st, ref, 1e-6, 1e-6, 1e-6, k)
 
 
 @pytest.fixture(scope="module", params=["c3", "c4", "c5s"])
@@ -423,6 +425,33 @@ def test_degenerate_random_windows_differ_by_conditioning_not_by_code_path(seed)
     eng.run_schedule([c[0] for c in random_windows.SCHEDULE], [c[1] for c in random_windows.SCHEDULE])
     free = eng.get_states()[0]
     assert min(rel_err(free, chains["banded"]), rel_err(free, chains["dense"])) < 10 * drift
+    eng.close()
+
+
+@pytest.mark.parametrize("seed", [315, 318])
+def test_long_edges_of_the_diverged_random_windows_against_the_exact_chain(seed):
+    """Seeds 315 and 318 of the randomised windows WITH long gaps diverge in the stress run (their
+    conditioning: tests/test_oracle_golden.py::test_conditioning_of_the_diverged_random_windows_with_long_gaps).  At the
+    oracle's states before the last call of the schedule -- where they diverged -- the factor of every long edge is within the
+    exact-chain bars of tests/test_gpu_long_gaps.py (EXACT_FACTOR x the fp64 serial walk's error + 2^-46, per component).  |Phi| over
+    the gaps there: seed 315 edges of 1250 / 1254 / 523 / 462 s: 1.5e3 / 1.4e3 / 5.4e2 / 1.0e7 (the last one passes close to
+    the Earth's centre: the serial walk itself is off the exact chain by 2e-11 in Phi); seed 318, 1038 / 117 / 610 s: 9.4e3 /
+    1.2e2 / 6.8e2 (its first pose starts 1 735 km from the centre)."""
+    import random_windows
+    from test_gpu_long_gaps import _check_factor_exact
+    from vinsat_amd.engine import BAEngine
+    win, xyz, uv, ii, conf, t, st0 = random_windows.make(seed, long_gaps=True)
+    args = (win.cumrot_last, uv, xyz, ii, t, win.intrinsics, conf)
+    st, lam = st0.copy(), 1e-4
+    for it, init in random_windows.SCHEDULE[:-1]:
+        st, lam, _, _ = O.ba_iteration(it, st, *args, lam, initialize=init)
+    n = win.time_idx.size
+    eng = BAEngine(n, ii.size)
+    eng.upload_observations(xyz, uv, conf, ii, n)
+    eng.upload_window(win.intrinsics, win.cumrot_last, t)
+    it, init = random_windows.SCHEDULE[-1]
+    eng.iterate(it, init, lam, st)
+    _check_factor_exact(eng, st, t, ("diverged", seed))
     eng.close()
 
 

@@ -11,6 +11,7 @@ import pytest
 
 from conftest import GOLDEN, golden_inputs, load_golden, rel_err
 from oracle import ba_oracle as O
+from state_metrics import assert_states
 
 pytestmark = pytest.mark.gpu
 
@@ -43,26 +44,8 @@ def _win_engine(win, f32, windows=1):
     return e
 
 
-def _state_errors(st, ref):
-    """(position max-rel, velocity max-rel, attitude angle in rad), each over the window."""
-    pos = np.abs(st[:, :3] - ref[:, :3]).max() / np.abs(ref[:, :3]).max()
-    vel = np.abs(st[:, 7:] - ref[:, 7:]).max() / np.abs(ref[:, 7:]).max()
-    q, qr = st[:, 3:7], ref[:, 3:7]     # (x, y, z, w)
-    q = q / np.linalg.norm(q, axis=1, keepdims=True)
-    qr = qr / np.linalg.norm(qr, axis=1, keepdims=True)
-    # q^-1 (x) q_ref: vector part and scalar part
-    w1, v1 = q[:, 3], -q[:, :3]
-    w2, v2 = qr[:, 3], qr[:, :3]
-    w = w1 * w2 - (v1 * v2).sum(1)
-    v = w1[:, None] * v2 + w2[:, None] * v1 + np.cross(v1, v2)
-    ang = 2 * np.arctan2(np.linalg.norm(v, axis=1), np.abs(w))
-    return float(pos), float(vel), float(ang.max())
-
-
 def _within_bars(st, ref, what):
-    e = _state_errors(st, ref)
-    assert e[0] <= BAR and e[1] <= BAR and e[2] <= BAR, (what, e)
-    return e
+    return assert_states(st, ref, BAR, BAR, BAR, what)
 
 
 def _row_err(J, Jref):

@@ -171,6 +171,26 @@ def test_conditioning_of_the_degenerate_random_windows(seed, degenerate):
     assert (drift > 1e-6) if degenerate else (drift < 1e-9), drift
 
 
+@pytest.mark.parametrize("seed,degenerate", [(0, False), (1, False), (2, False), (3, False), (315, True), (318, True)])
+def test_conditioning_of_the_diverged_random_windows_with_long_gaps(seed, degenerate):
+    """Evidence for DESIGN.md section 5 (stress run with long gaps): seeds 315 (27 poses, gaps of 1250 / 1254 / 523 / 462 s) and
+    318 (14 poses, 1038 / 117 / 610 s) of random_windows.make(seed, long_gaps=True) diverge on the GPU -- and the oracle's own
+    banded and dense LU drift apart over the same six calls there: 7e-2 (seed 315, LM steps of thousands of km) and 4.8e-6
+    (seed 318), against 4e-14 .. 1e-8 on seeds 0 .. 3 with long gaps."""
+    import random_windows
+    win, xyz, uv, ii, conf, t, st0 = random_windows.make(seed, long_gaps=True)
+    assert (O.step_counts(t) > 64).any()
+    ends = {}
+    for solver in ("banded", "dense"):
+        st, lam = st0.copy(), 1e-4
+        for it, init in random_windows.SCHEDULE:
+            st, lam, _, _ = O.ba_iteration(it, st, win.cumrot_last, uv, xyz, ii, t, win.intrinsics, conf, lam, initialize=init,
+                                           solver=solver)
+        ends[solver] = st
+    drift = np.abs(ends["banded"] - ends["dense"]).max() / np.abs(ends["dense"]).max()
+    assert (drift > 1e-6) if degenerate else (drift < 1e-7), drift
+
+
 def test_hop_integrator_chained_c2_run_of_the_reference():
     """tests/golden/hopc2.npz: the reference's driver on the C2 window with its GPU-default integrator -- predict_gpu's
     arithmetic: predict (BA_utils.py:457-527) with propagate_orbit_dynamics_skip (:52-71) in place of propagate_orbit_dynamics,

@@ -703,7 +703,8 @@ int vba_upload_window(vba_handle h, int window, int n, const double* intrinsics,
     std::vector<int> steps(n);
     for (int i = 0; i + 1 < n; ++i) {
         const int64_t d = time_idx[i + 1] - time_idx[i];
-        if (d < 1 || d > 100000000) return fail(VBA_EINVAL, "time_idx must be strictly increasing");
+        if (d < 1) return fail(VBA_EINVAL, "time_idx must be strictly increasing");
+        if (d > VBA_MAX_GAP) return fail(VBA_EINVAL, "time_idx: a gap longer than VBA_MAX_GAP (2^20 s)");
         steps[i] = (int)d;
     }
     steps[n - 1] = 1;   // BA_utils.py:75
@@ -716,7 +717,7 @@ int vba_upload_window(vba_handle h, int window, int n, const double* intrinsics,
     int nl = 0, pool_used = 0;
     for (int i = 0; i + 1 < n && nl < kLongCap; ++i)
         if (steps[i] > kLongGap) {
-            const int need_states = 3 + long_plan(steps[i]).G + 48;     // header, sub-chunk start states, eight 6x6 partial products (vba_long.hip)
+            const int need_states = long_pool_states(long_plan(steps[i]));
             if (pool_used + need_states > h->V.long_pool_cap) continue;
             long_list[kLongCap + 1 + nl] = pool_used;
             pool_used += need_states;

@@ -68,8 +68,9 @@ __device__ __forceinline__ void rk4_coarse(const double* x, double h, double hh,
 constexpr double kLongTight = 0x1p-48, kLongLoose = 0x1p-45;
 
 // One wavefront.  x0: the state at the start of the gap (the same in every lane), s: its steps.  Lane j < P ends up with the
-// converged chunk-start state U_j in `U`; xh (every lane) = U_P, the state at the end of the gap.  Everything lives in registers:
-// a lane keeps what concerns its chunk (its start state U, its end state N = the next chunk's start).
+// converged chunk-start state U_j in `U`; xh (every lane) = the state at the end of the gap, the last chunk's fine end state
+// F_{P-1}(U_{P-1}).  Everything lives in registers: a lane keeps what concerns its chunk (its start state U, its end state N = the
+// next chunk's start).
 // The correction sweep is LINEARISED: with A_j the Jacobian of the coarse step at U_j (every lane forms its own, six tangents
 // through one RK4 step) the parareal update G_j(U_j') - G_j(U_j) becomes A_j c_j and the sweep the affine recurrence
 //     c_0 = 0,  c_{j+1} = (F_j(U_j) - U_{j+1}) + A_j c_j,   U_j' = U_j + c_j
@@ -173,8 +174,10 @@ __device__ __forceinline__ void long_states(const double* x0, int s, const LongP
             }
         }
     }
+    // the end of the gap is where the last chunk's FINE pass landed (F of lane P - 1), not the corrected coarse state N: the loose
+    // stop rule leaves the two up to 2^-45 apart
 #pragma unroll
-    for (int c = 0; c < 6; ++c) xh[c] = readlane_f64(N[c], P - 1);
+    for (int c = 0; c < 6; ++c) xh[c] = readlane_f64(F[c], P - 1);
 }
 
 }  // namespace
@@ -183,6 +186,7 @@ __device__ __forceinline__ void long_states(const double* x0, int s, const LongP
 // sub-chunk start states, then kLongSplit partial products of the transition matrix (36 doubles each).
 constexpr int kLongHead = 3;
 constexpr int kLongSplit = 8;           // workgroups that share the tangent pass of one edge (16 sub-chunks each)
+static_assert(kLongHead == 3 && kLongSplit * 36 == 48 * 6, "long_pool_states (vba_math.h) sizes the slot the upload reserves");
 
 // where the chain of long edge k of window w lives for the call of parity `par` (every long edge has a slot: an edge the window's
 // pool has no room for is not marked long, vba_upload_window)

@@ -351,7 +351,7 @@ struct LongPlan { int L, P, sub, nsubL, G; };
 VBA_HD LongPlan long_plan(int s) {
     LongPlan p;
     int L = 1;
-    while (45 * L * L < 34 * s) ++L;
+    while (45LL * L * L < 34LL * s) ++L;       // (64-bit: 45 L^2 passes INT_MAX above s ~ 6.3e7)
     if (64 * L < s) L = (s + 63) / 64;
     p.L = L;
     p.P = (s + L - 1) / L;             // <= 64
@@ -363,6 +363,10 @@ VBA_HD LongPlan long_plan(int s) {
     p.G = (p.P - 1) * p.nsubL + (last + p.sub - 1) / p.sub;
     return p;
 }
+
+// states of six doubles that a long edge takes in its window's chain pool (vba_long.hip: long_slot): the header (3), the G sub-chunk
+// start states and eight 6x6 partial products of the transition matrix (48)
+VBA_HD int long_pool_states(const LongPlan& p) { return 3 + p.G + 48; }
 
 // ------------------------------------------------------------------------------------------------ attitude
 VBA_HD void quat_mul(const double* a, const double* b, double* o) {   // BA_utils.py:992-1000
