@@ -44,6 +44,7 @@ enum {
     VBA_FLAG_LAMBDA_EXHAUSTED = 1u, /* "lamda too large": no trial improved, last trial kept (BA_filtering.py:75-77) */
     VBA_FLAG_NONFINITE = 2u,        /* NaN/Inf met in the solve or the residuals */
     VBA_FLAG_ZERO_PIVOT = 4u,       /* a diagonal block was numerically singular */
+    VBA_FLAG_INDEFINITE = 8u,       /* vba_covariance only: a pivot of the symmetric block elimination was negative (not positive definite) */
     VBA_FLAG_HOST_CHANGED = 1u << 30 /* vba_iterate_resident only: a watched host buffer (vba_set_host_watch) no longer holds the bytes
                                        that were uploaded -- the result was computed from the OLD window: upload again and repeat the call */
 };
@@ -285,6 +286,31 @@ int vba_pipeline_stats(vba_handle h, int* hits, int* discards);
 /* Copy an intermediate of the last step of `window` to host memory; *count receives the number of
  * doubles written (capacity is checked). */
 int vba_debug_fetch(vba_handle h, int window, int what, double* out, int64_t capacity, int64_t* count);
+
+/* ---- per-pose marginal covariances.  For every window, at the RESIDENT states (what the last call returned), the full-phase
+ * system a vba_step(h, iter, 0) would factor there: the observation, dynamics and attitude factors (long gaps and the integrator as
+ * set), and the BA_reg prior if vba_set_prior(h, 1) is on.
+ *   A      the undamped bands as VBA_DBG_BANDS defines them; damped != 0 adds float32(lamda_resident) I, the damping the next
+ *          call's first trial would use (BA_filtering.py:54) -- that matrix is the reference's JTwJ;
+ *   A^     (A + A^T) / 2: A is symmetric but for the 3x3 rot-rot diagonal blocks Sigma Hd of the attitude factor;
+ *   diag   [W][n_max][9][9]  Sigma_ii = (A^-1)_ii, exactly symmetric (one triangle computed, mirrored);
+ *   super  [W][n_max][9][9]  Sigma_i,i+1 = (A^-1)_i,i+1 for i < n - 1 (zeros for i = n - 1 and for rows beyond n);
+ *   flags  [W]  VBA_FLAG_ZERO_PIVOT: numerically singular (e.g. the velocities of a one-pose window, undamped): that window's blocks
+ *               are NaN; VBA_FLAG_INDEFINITE: the blocks are returned but are no covariance; VBA_FLAG_NONFINITE as elsewhere.
+ * Any of diag / super / flags may be NULL.  Coordinates are those of the step dpose: [dp (km), dtheta, dv (km/s)], where dtheta
+ * linearises a rotation of angle 2 |dtheta| (the retraction q (x) [dtheta, 1], normalised): the attitude sigma in radians is
+ * 2 sqrt(Sigma_theta).  The robust weights are normalised by their maximum w_max, so Sigma is a covariance up to a scale factor
+ * that this library does not estimate (no a-posteriori variance factor).
+ * Algorithm: block LDL^T and selected inversion (csrc/vba_cov.hip), fp64; the path follows vba_set_solver: chunk 0 one wavefront
+ * walks each window, a chunked setting eliminates the same chunks in parallel and inverts the separator system (the two agree to
+ * rounding, ~1e-10).  The system is built by the kernels of a call's front into scratch of the query.  The query changes nothing: states, lamda, flags, carried keys, schedule
+ * graphs and the long-gap chain pool stay as they were, the following calls give the same bits; a speculated call of the
+ * pipelined loop is dropped as a mismatched resident call drops it.  Scratch is allocated on the first query (about
+ * 700 doubles per pose and 5 per observation row, per window, plus a copy of the long-gap chain pool).  VBA_ESTATE before every window has states,
+ * and on observation-sharded handles.  Synchronous. */
+int vba_covariance(vba_handle h, int iter, int damped, double* diag, double* super, unsigned* flags);
+/* HIP-event time of the last vba_covariance on the handle's stream (front + inversion), milliseconds. */
+int vba_last_covariance_ms(vba_handle h, float* ms);
 
 /* Timing of the last vba_step measured with HIP events on the handle's stream, milliseconds. */
 int vba_last_step_ms(vba_handle h, float* ms);

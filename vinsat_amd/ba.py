@@ -565,6 +565,7 @@ def BA(iter, states, velocities, imu_meas, landmarks, landmarks_xyz, ii, time_id
         st, lams, hs, ntr, flags = _BA_batched([iter], [initialize], states, velocities, imu_meas, landmarks, landmarks_xyz, ii,
                                                time_idx, intrinsics, confidences, lamda_init, device)
         BA.last = dict(n_trials=ntr, flags=flags)
+        _cache["last_query"] = dict(eng="beng", iter=int(iter), reg=False, form=_cache["bform"], ns=list(_cache["bns"]))
         return (st, velocities, lams, hs)
     shp = states.shape
     if len(shp) != 3 or shp[0] != 1 or shp[2] != 10:
@@ -578,6 +579,7 @@ def BA(iter, states, velocities, imu_meas, landmarks, landmarks_xyz, ii, time_id
     if flags & 1:
         print("lamda too large")          # reference BA_filtering.py:76
     BA.last = dict(n_trials=n_trials, flags=flags)
+    _cache["last_query"] = dict(eng="eng", iter=int(iter), reg=False, form="single", ns=[n])
     st, hs = _wrap(out, lam, hess, False)
     return (st, velocities, lam, hs)
 
@@ -617,6 +619,7 @@ def BA_reg(iter, states, velocities, states_prior, velocity_prior, hessian_state
     if flags & 1:
         print("lamda too large")          # reference BA_filtering.py:186
     BA_reg.last = dict(n_trials=n_trials, flags=flags)
+    _cache["last_query"] = dict(eng="eng", iter=int(iter), reg=True, form="single", ns=[n])
     st, hs = _wrap(out, lam, hess, True)
     return (st, velocities, lam, hs)
 
@@ -637,6 +640,7 @@ def BA_window(iters, initializes, states, velocities, imu_meas, landmarks, landm
         st, lams, hs, ntr, flags = _BA_batched(list(iters), list(initializes), states, velocities, imu_meas, landmarks,
                                                landmarks_xyz, ii, time_idx, intrinsics, confidences, lamda_init, device)
         BA_window.last = dict(n_trials=ntr, flags=flags)
+        _cache["last_query"] = dict(eng="beng", iter=int(list(iters)[-1]), reg=False, form=_cache["bform"], ns=list(_cache["bns"]))
         return (st, velocities, lams, hs)
     n = _shape_of(states)
     # (vba_run_schedule does not evaluate the host watch: an ndarray edited in place since the upload is looked for here)
@@ -647,8 +651,72 @@ def BA_window(iters, initializes, states, velocities, imu_meas, landmarks, landm
     out, lam, hess, n_trials, flags = eng.get_states()
     if flags & 1:
         print("lamda too large")
+    _cache["last_query"] = dict(eng="eng", iter=int(list(iters)[-1]), reg=False, form="single", ns=[n])
     st, hs = _wrap(out, lam, hess, False)
     return (st, velocities, lam, hs)
 
 
 BA_window.last = {}
+
+
+# ------------------------------------------------------------------------------------------------ uncertainty
+def covariance(iter=None, damped=False, super_diagonal=False):
+    """Marginal covariances of the poses at the states the last :func:`BA` / :func:`BA_reg` / :func:`BA_window` call returned
+    (``vba_covariance``, ``include/vinsat_ba.h``): the diagonal blocks ``Sigma_ii`` -- and with ``super_diagonal`` the blocks
+    ``Sigma_i,i+1`` -- of the inverse of the symmetrised full-phase normal matrix a ``BA(iter)`` call would build there.
+    ``iter`` defaults to that call's ``iter`` (its last one for ``BA_window``); the prior is included iff that call was
+    ``BA_reg``; ``damped`` adds the damping the next call would start with (the reference's ``JTwJ``).  Coordinates of the
+    step: [dp (km), dtheta, dv (km/s)] (attitude sigma = 2 sqrt(Sigma_theta), :func:`pose_sigmas`).  Up to the scale of the
+    robust weights, which are normalised by their maximum.
+
+    Shapes follow the last call's form: ``[1, n, 9, 9]`` for one window, ``[B, n, 9, 9]`` for a dense batch, a list of
+    ``[1, n_b, 9, 9]`` for a ragged one (fp64 torch tensors).  ``covariance.last["flags"]``: the ``VBA_FLAG_*`` bits per window
+    (4: singular -- that window's blocks are NaN; 8: indefinite -- no covariance).  The device states, damping and the bits of
+    the following calls are not changed."""
+    import torch
+    q = _cache.get("last_query")
+    eng = _cache.get(q["eng"]) if q is not None else None
+    if eng is None or not getattr(eng, "h", None):
+        raise RuntimeError("covariance() needs a preceding BA / BA_reg / BA_window call")
+    it = q["iter"] if iter is None else int(iter)
+    if q["reg"]:
+        eng.set_prior(True)
+    try:
+        res = eng.covariance(it, damped=damped, super_diagonal=super_diagonal)
+    finally:
+        if q["reg"]:
+            eng.set_prior(False)
+    diag, sup, flags = res if super_diagonal else (res[0], None, res[1])
+    ns, form = q["ns"], q["form"]
+
+    def shaped(a):
+        if a is None:
+            return None
+        if form == "single":
+            return torch.from_numpy(np.ascontiguousarray(a[:1, :ns[0]]))
+        if form == "dense":
+            return torch.from_numpy(np.ascontiguousarray(a[:len(ns), :ns[0]]))
+        return [torch.from_numpy(np.ascontiguousarray(a[b:b + 1, :n])) for b, n in enumerate(ns)]
+
+    fl = [int(x) for x in flags[:len(ns)]]
+    covariance.last = dict(flags=fl[0] if form == "single" else fl)
+    return (shaped(diag), shaped(sup)) if super_diagonal else shaped(diag)
+
+
+covariance.last = {}
+
+
+def pose_sigmas(cov):
+    """1-sigma per pose from marginal blocks ``cov [..., n, 9, 9]`` (:func:`covariance`): ``(position [..., n, 3] km,
+    velocity [..., n, 3] km/s, attitude [..., n, 3] rad)``.  The step's ``dtheta`` linearises a rotation of angle ``2 dtheta``,
+    so the attitude sigma is ``2 sqrt(Sigma_theta)``.  A list (ragged batch) gives a list of tuples; torch in, torch out."""
+    if isinstance(cov, (list, tuple)):
+        return [pose_sigmas(c) for c in cov]
+    is_torch = not isinstance(cov, np.ndarray)
+    a = _np(cov) if is_torch else cov
+    d = np.diagonal(a, axis1=-2, axis2=-1)
+    pos, att, vel = np.sqrt(d[..., 0:3]), 2.0 * np.sqrt(d[..., 3:6]), np.sqrt(d[..., 6:9])
+    if is_torch:
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(pos)), torch.from_numpy(np.ascontiguousarray(vel)), torch.from_numpy(np.ascontiguousarray(att))
+    return pos, vel, att

@@ -107,7 +107,7 @@ static int vba_set_accumulate_lanes(vba_handle h, int lanes);
 static int vba_set_trial_tiles(vba_handle h, int tiles);
 int vba_set_solver(vba_handle h, int chunk);
 
-int vba_version(void) { return 220; }     // 2.2: VBA_OPT_JACOBIAN_F32 (2.1: vba_set_chunk_waves, fusion bits 2..4, warm select mode 3)
+int vba_version(void) { return 230; }     // 2.3: vba_covariance; 2.2: VBA_OPT_JACOBIAN_F32 (2.1: vba_set_chunk_waves, fusion bits 2..4, warm select mode 3)
 
 const char* vba_last_error(void) { return g_err.c_str(); }
 
@@ -402,6 +402,8 @@ int vba_destroy(vba_handle h) {
     if (h->h_back) hipHostFree(h->h_back);
     if (h->h_head) hipHostFree(h->h_head);
     if (h->d_dbg) hipFree(h->d_dbg);
+    if (h->d_cov) hipFree(h->d_cov);
+    for (hipEvent_t e : h->cov_ev) if (e) hipEventDestroy(e);
     if (h->arena.base) hipFree(h->arena.base);
     delete h;
     return VBA_OK;

@@ -4,6 +4,7 @@
 //   vba_schedule.hip     the kernels of one BA() call as the host enqueues them: vba_step, vba_run_schedule (chained calls, graph
 //                        replay), vba_iterate* (pipelined driver loop, host watch)
 //   vba_sharded_api.hip  observation-sharded mode (vba_sh_*)
+//   vba_cov.hip          per-pose marginal covariances (vba_covariance)
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -148,6 +149,13 @@ struct vba_context {
     int warm_misses = 0;                    // number of calls whose warm select missed and was repeated with the exact digits (diagnostic)
     double* d_dbg = nullptr;                // lazily allocated scratch for debug fetch
     size_t dbg_cap = 0;
+    // vba_covariance (vba_cov.hip): scratch allocated by the first query, its events and the time of the last query
+    void* d_cov = nullptr;
+    size_t cov_cap = 0;
+    hipEvent_t cov_ev[2] = {nullptr, nullptr};
+    float cov_ms = 0.f;
+    bool cov_ran = false;
+    bool sharded = false;                   // an observation-sharded call has run (vba_sh_*): no covariance query
     // Pipelined driver loop (vba_iterate_resident, see iterate_pipelined): the call that was enqueued speculatively behind
     // the one that has just been returned, the chain it belongs to and what has been learnt about the caller's schedule
     struct Spec { bool valid = false; int iter = 0, init = 0; bool reg = false; int c = 0; } spec;

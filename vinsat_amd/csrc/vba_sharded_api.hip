@@ -29,6 +29,7 @@ int vba_sh_stage1(vba_handle h, int iter, int initialize, int64_t m_total, doubl
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     h->V.m_total = m_total;
+    h->sharded = true;
     h->last_iter = iter;
     h->last_init = initialize;
     h->carry_ok = false;
@@ -151,6 +152,7 @@ int vba_sh_comm_init(vba_handle h, const char* rccl_path, const void* id128, int
     if (int rc_settle = settle(h)) return rc_settle;
     if (h->W != 1) return fail(VBA_EINVAL, "sharded mode uses a single window per handle");
     if (h->shc.comm) return fail(VBA_ESTATE, "the handle has a communicator already");
+    h->sharded = true;
     HIPCHK(hipSetDevice(h->device));
     auto& S = h->shc;
     S.dl = open_rccl(rccl_path);

@@ -277,6 +277,27 @@ class BAEngine:
         _lib.check(self.lib.vba_last_step_ms(self.h, byref(ms)), self.lib)
         return ms.value
 
+    FLAG_ZERO_PIVOT, FLAG_NONFINITE, FLAG_INDEFINITE = 4, 2, 8
+
+    def covariance(self, it, damped=False, super_diagonal=False):
+        """``vba_covariance``: marginal covariances of every window at the resident states (``include/vinsat_ba.h``).
+
+        Returns ``(diag, flags)`` -- or ``(diag, super, flags)`` with ``super_diagonal`` -- where ``diag [W, n_max, 9, 9]`` holds
+        the blocks Sigma_ii of the inverse of the symmetrised full-phase system of a ``BA(it)`` call, ``super [W, n_max, 9, 9]``
+        the blocks Sigma_i,i+1 and ``flags [W]`` the ``VBA_FLAG_*`` bits of each window.  Coordinates: [dp (km), dtheta, dv (km/s)]."""
+        W, N = self.windows, self.n_max
+        diag = np.empty((W, N, 9, 9))
+        sup = np.empty((W, N, 9, 9)) if super_diagonal else None
+        flags = np.empty(W, dtype=np.uint32)
+        _lib.check(self.lib.vba_covariance(self.h, int(it), int(bool(damped)), _p(diag), _p(sup) if sup is not None else None,
+                                           flags.ctypes.data_as(ctypes.POINTER(c_uint))), self.lib)
+        return (diag, sup, flags) if super_diagonal else (diag, flags)
+
+    def last_covariance_ms(self):
+        ms = c_float()
+        _lib.check(self.lib.vba_last_covariance_ms(self.h, byref(ms)), self.lib)
+        return ms.value
+
     def debug(self, what, window=0):
         n, m = self.n[window], self.m[window]
         shapes = dict(est=(m, 2), weight=(m,), H=(n, 6, 6), b=(n, 6), Phi=(n, 6, 6), r_pred=(n - 1, 7), qgrad=(n, 3),

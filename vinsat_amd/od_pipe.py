@@ -401,7 +401,7 @@ class _Clock:
 
 
 def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, detections_file_name=None,
-                      ba=None, num_iters=NUM_ITERS, record=None, timing=None, run=None, device=0):
+                      ba=None, num_iters=NUM_ITERS, record=None, timing=None, run=None, device=0, covariances=None):
     """Drop-in for the reference's ``streaming_version`` (od_pipe.py:911-1062).
 
     ``ba`` defaults to the HIP-backed :func:`vinsat_amd.ba.BA`; tests may inject another
@@ -410,7 +410,12 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
     ``timing`` (a dict) receives the wall time by phase (:class:`_Clock`).  ``run``: a :class:`SequenceRun` prepared elsewhere
     (:func:`prepared_runs`) instead of the input arrays / files.  With the default ``ba`` the per-row part of the data preparation
     runs on GPU ``device`` as well (:func:`prepare_window`); an injected ``ba`` keeps the preparation on the host.
+    ``covariances`` (a list) receives, after every batch, the marginal covariance ``[9, 9]`` of the batch's last pose at its final
+    states (:func:`vinsat_amd.ba.covariance`: [dp km, dtheta, dv km/s]) -- the pose whose error ``finish_patch`` records; it
+    needs the default ``ba`` and leaves the estimates bit for bit as they are without it.
     """
+    if covariances is not None and ba is not None:
+        raise ValueError("covariances needs the default (HIP) ba")
     ba_window = None
     rows_device = None
     if ba is None:
@@ -441,13 +446,17 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
             if record is not None:
                 record.append(dict(patch=run.patch, iter=it, states=states_t.clone(), lamda=lam))
         t0 = clk("ba", t0, num_iters)
+        if covariances is not None:
+            from .ba import covariance
+            covariances.append(covariance()[0, -1].clone())
+            t0 = clk("bookkeeping", t0)
         run.finish_patch(states_t, vel_t)
     out = run.result()
     clk("bookkeeping", t0)
     return out
 
 
-def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=None, timing=None, threads=None, device=0):
+def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=None, timing=None, threads=None, device=0, covariances=None):
     """Many sequences at once -- the reference's outer loop over sequence files (od_pipe.py:1069-1077) turned into the batch
     dimension of ``BA``: round r runs batch r of EVERY sequence that still has one as the windows of ONE ragged handle
     (:func:`vinsat_amd.ba.BA_window` on lists: every kernel launch covers all of them), sequences that have ended drop out.
@@ -455,8 +464,12 @@ def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=Non
     ``sequences``: list of ``(detections, orbit_np)`` pairs.  Returns the list of ``streaming_version`` results.  With equal
     handle settings (``vinsat_amd.ba.configure``) every sequence gets the bits of its own ``streaming_version`` run.
     ``record`` (a list) receives ``dict(round, sequence, states, lamda)`` after every round; ``timing`` (a dict) the wall time
-    by phase (:class:`_Clock`).
+    by phase (:class:`_Clock`).  ``covariances`` (a list) receives ``dict(round, sequence, cov)`` after every round: ``cov`` the
+    marginal covariance ``[9, 9]`` of the last pose of that sequence's batch (:func:`vinsat_amd.ba.covariance`); it needs the
+    default ``ba_window`` and changes no result.
     """
+    if covariances is not None and ba_window is not None:
+        raise ValueError("covariances needs the default (HIP) ba_window")
     rows_device = None
     if ba_window is None:
         rows_device = device            # (the HIP BA is in use: the per-row preparation runs on its device as well)
@@ -489,6 +502,13 @@ def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=Non
                                       [p["time_idx"] for p in ps], [p["intr"] for p in ps], [p["conf"] for p in ps],
                                       [p["lam"] for p in ps])
         t0 = clk("ba", t0, num_iters * len(ps))
+        if covariances is not None:
+            from .ba import covariance
+            cov = covariance()
+            cov = cov if isinstance(cov, list) else [cov]
+            for (k, _, _), c in zip(live, cov):
+                covariances.append(dict(round=rnd, sequence=k, cov=c[0, -1].clone()))
+            t0 = clk("bookkeeping", t0)
         for (k, r, p), s_new, l_new in zip(live, st, lam):
             if record is not None:
                 record.append(dict(round=rnd, sequence=k, states=s_new.clone(), lamda=l_new))
