@@ -959,7 +959,7 @@ int vba_debug_fetch(vba_handle h, int window, int what, double* out, int64_t cap
             *count = 64;
             return VBA_OK;
         }
-        case 101: {         // ... and of one thread along the solve kernels (g_kstamps, vba_solve.hip): 128 raw words
+        case 101: {         // ... and of one thread along the solve kernels (g_kstamps, vba_solve_step.h): 128 raw words
             if (capacity < 128) return fail(VBA_EINVAL, "debug buffer too small");
             fetch_kstamps(reinterpret_cast<unsigned long long*>(out));
             *count = 128;

@@ -12,20 +12,13 @@
 //   backward  S_n-1 = D_n-1^-1,  S_i,i+1 = -Y_i S_i+1,  S_ii = D_i^-1 - S_i,i+1 Y_i^T
 // Two paths, chosen by the solver setting of the handle (vba_set_solver): the sequential walk, one wavefront per window (k_cov_seq);
 // the partitioned path over the solver's chunks (k_cov_chunk, k_cov_sep, k_cov_fix; see there).  Lane c owns column c of [D_i | B_i | I] (27 columns): the Gauss-Jordan elimination of that
-// augmented block leaves Y_i in lanes 9..17 and D_i^-1 in lanes 18..26 -- the solve's own step (vba_solve.hip) with nine identity
+// augmented block leaves Y_i in lanes 9..17 and D_i^-1 in lanes 18..26 -- the solve's own step (vba_solve_step.h) with nine identity
 // right-hand sides in its idle lanes.  The pivot row is read with v_readlane (one system per wave: the row is uniform).  Y_i and
 // D_i^-1 are kept in the two output arrays and overwritten by S_i,i+1 and S_ii in the backward sweep.
 #include "vba_context.h"
 #include "vba_step.h"
 
 namespace vba {
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    const unsigned long long b = f64_bits(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-    return bits_f64(((unsigned long long)hi << 32) | lo);
-}
 
 // The selected inversion of one block-tridiagonal chain by one wavefront: bw [n_rows][3][81] (sub, diag, super; row-major blocks) of
 // which the first n are poses, A^ = (A + A^T) / 2 + lam32 I.  Dw / Sw [n_rows][81]: S_ii and S_i,i+1 (rows >= n and the super block of
@@ -87,7 +80,7 @@ __device__ unsigned cov_walk(const double* __restrict__ bw, int n, int n_rows, d
             if (!(fabs(piv) <= 1.79e308)) fl |= VBA_FLAG_NONFINITE;
             else if (!(fabs(piv) > 1e-10 * fabs(d0[k]))) fl |= VBA_FLAG_ZERO_PIVOT;
             else if (piv < 0.0) fl |= VBA_FLAG_INDEFINITE;
-            a[k] *= step_fast_rcp(piv);
+            a[k] *= fast_rcp(piv);
 #pragma unroll
             for (int r = 0; r < 9; ++r)
                 if (r != k) a[r] = fma(-f[r], a[k], a[r]);
@@ -293,7 +286,7 @@ __global__ __launch_bounds__(64) void k_cov_chunk(const double* __restrict__ ban
             if (!(fabs(piv) <= 1.79e308)) fl |= VBA_FLAG_NONFINITE;
             else if (!(fabs(piv) > 1e-10 * fabs(d0[k]))) fl |= VBA_FLAG_ZERO_PIVOT;
             else if (piv < 0.0) fl |= VBA_FLAG_INDEFINITE;
-            a[k] *= step_fast_rcp(piv);
+            a[k] *= fast_rcp(piv);
 #pragma unroll
             for (int r = 0; r < 9; ++r)
                 if (r != k) a[r] = fma(-f[r], a[k], a[r]);

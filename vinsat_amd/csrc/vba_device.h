@@ -420,6 +420,26 @@ __device__ __forceinline__ void dpp_rank1_9(double (&A)[9], double (&B)[9]) {
 template <int K>
 __device__ __forceinline__ int bcast_row16_i32(int v) { return __builtin_amdgcn_mov_dpp(v, 0x150 + K, 0xf, 0xf, false); }
 
+// Lane `lane` (wave uniform) of the wavefront, to every lane: two v_readlane through scalar registers
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    const unsigned long long b = f64_bits(v);
+    const unsigned lo = __builtin_amdgcn_readlane((unsigned)b, lane);
+    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(b >> 32), lane);
+    return bits_f64(((unsigned long long)hi << 32) | lo);
+}
+
+// 1/x to ~1 ulp from v_rcp_f64's 24-bit seed (the full IEEE division sequence is 3x longer and sits on the
+// critical path of every pivot)
+__device__ __forceinline__ double fast_rcp(double x) {
+    // 1/x = r / (1 - e) with e = 1 - x r ~ 4e-8: r (1 + e + e^2) is exact to e^3, three dependent operations after the
+    // seed instead of the four of two Newton steps
+    double r = __builtin_amdgcn_rcp(x);
+    const double e = fma(-x, r, 1.0);
+    const double t = fma(e, e, e);
+    r = fma(r, t, r);
+    return r;
+}
+
 
 // Resolve one radix-select digit: given the histogram of digit p among keys matching the prefix and the
 // rank wanted inside that set, every thread of the block gets (new prefix, new rank).  256 threads.

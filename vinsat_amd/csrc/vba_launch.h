@@ -30,10 +30,10 @@ void launch_assemble(const DevView& V, int fuse_init_solve, hipStream_t s);
 void launch_long_factor(const DevView& V, hipStream_t s);
 void launch_long_trial(const DevView& V, hipStream_t s);
 
-// vba_solve.hip
+// vba_solve.hip (the dispatch over the solver units vba_solve_*.hip; their own launchers: vba_solve_units.h)
 void launch_solve(const DevView& V, int initialize, hipStream_t s);
 #ifdef VBA_RESIDENT_STAMPS
-void fetch_kstamps(unsigned long long* out);     // diagnostic builds: see vba_solve.hip
+void fetch_kstamps(unsigned long long* out);     // diagnostic builds: see VBA_KSTAMP, vba_solve_step.h
 void fetch_ostamps(unsigned long long* out);     // ... and vba_obs.hip
 #endif
 hipError_t configure_solver_device();      // per device, from vba_create

@@ -34,13 +34,6 @@ namespace vba {
 
 namespace {
 
-__device__ __forceinline__ double readlane_f64(double v, int lane /*wave-uniform*/) {
-    const unsigned long long b = f64_bits(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-    return bits_f64(((unsigned long long)hi << 32) | lo);
-}
-
 // the coarse propagator: one RK4 step of length h (hh = h / 2, h6 = h / 6 precomputed: an IEEE division per step would sit on
 // the critical path of the sweep)
 __device__ __forceinline__ void rk4_coarse(const double* x, double h, double hh, double h6, double* o) {

@@ -12,15 +12,6 @@
 
 namespace vba {
 
-// 1/x to ~1 ulp from v_rcp_f64's seed: r (1 + e + e^2), e = 1 - x r (three dependent operations)
-__device__ __forceinline__ double step_fast_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r, 1.0);
-    const double t = fma(e, e, e);
-    r = fma(r, t, r);
-    return r;
-}
-
 // Landmark-only phase (BA_utils.py:463-466: no dynamics factor): the system is block diagonal and inside a pose the
 // velocity rows carry only the damping, so the step of a pose solves (H_i / w_max + lam32 I) x = b_i / w_max (6x6,
 // Gauss-Jordan without row exchanges, every pivot checked against the diagonal entry it started from as in the chain
@@ -38,7 +29,7 @@ __device__ __forceinline__ bool step_blockdiag6(const double* H, const double* b
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
         if (!(A[k][k] > 1e-10 * d0[k])) ok = false;
-        const double inv = step_fast_rcp(A[k][k]);
+        const double inv = fast_rcp(A[k][k]);
 #pragma unroll
         for (int c = 0; c < 7; ++c) A[k][c] *= inv;
 #pragma unroll
@@ -92,7 +83,7 @@ __device__ __forceinline__ void step_blockdiag6_pivots(double (&a)[6], double d0
     if constexpr (K < 6) {
         const double piv = bcast_row16<K>(a[K]);
         if (l16 == K && !(piv > 1e-10 * d0)) ok = false;
-        const double inv = step_fast_rcp(piv);
+        const double inv = fast_rcp(piv);
         double f[6];
 #pragma unroll
         for (int r = 0; r < 6; ++r) f[r] = (r != K) ? bcast_row16<K>(a[r]) : 0.0;
