@@ -312,6 +312,40 @@ int vba_covariance(vba_handle h, int iter, int damped, double* diag, double* sup
 /* HIP-event time of the last vba_covariance on the handle's stream (front + inversion), milliseconds. */
 int vba_last_covariance_ms(vba_handle h, float* ms);
 
+/* ---- observation reliability: per row, how much of the fit hangs on it (leverage) and how far its residual lies from what the
+ * model predicts for it (standardised residual, Baarda's w-test).  At the RESIDENT states, for a full-phase call BA(iter), with
+ * the system of vba_covariance(h, iter, damped, ...): the same A^, the same damping and symmetrisation rules, Sigma = A^^-1.  For
+ * observation row k of pose i = ii[k]:
+ *   J_k [2,6]  the reprojection Jacobian over [dp, dtheta], as VBA_DBG_JG;
+ *   r_k [2]    the residual uv - est;
+ *   w_k        the final robust weight (w_raw / w_max) conf, as VBA_DBG_WEIGHT;
+ *   S_i        Sigma_ii[:6, :6];
+ *   P_k        w_k J_k S_i J_k^T (2x2); only its symmetric part is formed;
+ *   leverage [W][m_max]  tr(P_k), in [0, 2); the redundancy of the row is 2 - leverage;
+ *   wtest    [W][m_max]  sqrt(w_k r_k^T (I - P_k)^-1 r_k), the 2x2 inverse in closed form.  (I - P_k) / w_k is the covariance of the
+ *                        row's residual under the linearised model.  Unitless, in units of the same unestimated variance factor
+ *                        that vba_covariance documents;
+ *   pose_stats [W][n_max][3]  per pose: the sum of leverage over its rows (= tr(S_i H_i), H_i as VBA_DBG_H), the largest finite
+ *                        wtest of its rows, the count of its rows with w_k > 0; poses without rows get 0, 0, 0;
+ *   flags [W]  the flags of the covariance step (see vba_covariance).
+ * Both row arrays are in the INPUT order of the rows (the order of vba_upload_observations).  Degenerate rows are flagged in the
+ * value, not hidden: w_k == 0 gives leverage = 0, wtest = 0; det(I - P_k) <= 0 or a negative quadratic form gives wtest = NaN; a
+ * window flagged VBA_FLAG_ZERO_PIVOT / VBA_FLAG_NONFINITE has no Sigma: wtest = NaN for every row of it (those of weight zero
+ * included), leverage = NaN for its rows of non-zero weight (and so is the pose's sum).
+ * Any output may be NULL, in every combination; rows beyond a window's m and poses beyond its n are left untouched.
+ * Precision: with VBA_OPT_JACOBIAN_F32 = 1 the row pass still evaluates J_k in fp64 (the query is a diagnostic, not the hot loop);
+ * Sigma comes from the system the handle builds in its mode, as in vba_covariance.
+ * Algorithm: the shadow front and the selected inversion of vba_covariance into the scratch of the query, then one streaming pass
+ * over the rows (csrc/vba_rel.hip): no atomics, equal settings give equal bits, and a window has the same bits alone and in a batch.
+ * The promises are those of vba_covariance: the query changes nothing (states, lamda, flags, carried keys, schedule graphs, long-gap
+ * pool), drops a speculated pipelined call as a mismatched resident call does, returns VBA_ESTATE before every window has states
+ * and on observation-sharded handles, and is synchronous.  Scratch beyond the covariance query's is allocated on the first
+ * reliability query: two doubles and an index per observation row and window, whichever outputs are asked for (W = 4096 windows
+ * of 50 000 rows: 1.6 GB per row array); VBA_ENOMEM if that fails.  Only the non-NULL outputs are copied to the host. */
+int vba_reliability(vba_handle h, int iter, int damped, double* leverage, double* wtest, double* pose_stats, unsigned* flags);
+/* HIP-event time of the last vba_reliability on the handle's stream (front + inversion + row pass), milliseconds. */
+int vba_last_reliability_ms(vba_handle h, float* ms);
+
 /* Timing of the last vba_step measured with HIP events on the handle's stream, milliseconds. */
 int vba_last_step_ms(vba_handle h, float* ms);
 

@@ -706,6 +706,49 @@ def covariance(iter=None, damped=False, super_diagonal=False):
 covariance.last = {}
 
 
+def reliability(iter=None, damped=False):
+    """Observation reliability at the states the last :func:`BA` / :func:`BA_reg` / :func:`BA_window` call returned
+    (``vba_reliability``, ``include/vinsat_ba.h``): per row the leverage ``tr(P_k)``, ``P_k = w_k J_k S_i J_k^T`` with ``S_i`` the
+    pose's block of :func:`covariance`, and the standardised residual (w-test) ``sqrt(w_k r_k^T (I - P_k)^-1 r_k)``, both in the
+    order of the rows as they were passed in.  ``iter`` defaults to that call's ``iter`` (its last one for ``BA_window``); the
+    prior is included iff that call was ``BA_reg``; ``damped`` as in :func:`covariance`.  Up to the same unestimated variance
+    factor as :func:`covariance`; a row of weight zero gives 0, 0, a degenerate row or a window without a covariance NaN.
+
+    Returns ``(leverage, wtest)``: ``[1, m]`` tensors for one window, ``[B, m]`` for a dense batch, lists of ``[1, m_b]`` for a ragged
+    one (fp64).  ``reliability.last["flags"]``: the ``VBA_FLAG_*`` bits per window as ``covariance.last``; ``["pose_stats"]``: per
+    pose the sum of its leverages, its largest finite ``wtest``, its count of rows with non-zero weight (``[1, n, 3]`` / ``[B, n, 3]``
+    / a list).  The device states, damping and the bits of the following calls are not changed."""
+    import torch
+    q = _cache.get("last_query")
+    eng = _cache.get(q["eng"]) if q is not None else None
+    if eng is None or not getattr(eng, "h", None):
+        raise RuntimeError("reliability() needs a preceding BA / BA_reg / BA_window call")
+    it = q["iter"] if iter is None else int(iter)
+    if q["reg"]:
+        eng.set_prior(True)
+    try:
+        lev, wt, ps, flags = eng.reliability(it, damped=damped, pose_stats=True)
+    finally:
+        if q["reg"]:
+            eng.set_prior(False)
+    ns, form = q["ns"], q["form"]
+    ms = [int(eng.m[b]) for b in range(len(ns))]
+
+    def shaped(a, counts):
+        if form == "single":
+            return torch.from_numpy(np.ascontiguousarray(a[:1, :counts[0]]))
+        if form == "dense":
+            return torch.from_numpy(np.ascontiguousarray(a[:len(counts), :counts[0]]))
+        return [torch.from_numpy(np.ascontiguousarray(a[b:b + 1, :c])) for b, c in enumerate(counts)]
+
+    fl = [int(x) for x in flags[:len(ns)]]
+    reliability.last = dict(flags=fl[0] if form == "single" else fl, pose_stats=shaped(ps, ns))
+    return shaped(lev, ms), shaped(wt, ms)
+
+
+reliability.last = {}
+
+
 def pose_sigmas(cov):
     """1-sigma per pose from marginal blocks ``cov [..., n, 9, 9]`` (:func:`covariance`): ``(position [..., n, 3] km,
     velocity [..., n, 3] km/s, attitude [..., n, 3] rad)``.  The step's ``dtheta`` linearises a rotation of angle ``2 dtheta``,

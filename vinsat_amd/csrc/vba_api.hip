@@ -403,6 +403,8 @@ int vba_destroy(vba_handle h) {
     if (h->h_head) hipHostFree(h->h_head);
     if (h->d_dbg) hipFree(h->d_dbg);
     if (h->d_cov) hipFree(h->d_cov);
+    if (h->d_rel) hipFree(h->d_rel);
+    if (h->rel_ev) hipEventDestroy(h->rel_ev);
     for (hipEvent_t e : h->cov_ev) if (e) hipEventDestroy(e);
     if (h->arena.base) hipFree(h->arena.base);
     delete h;
@@ -658,6 +660,7 @@ int vba_upload_observations(vba_handle h, int window, int n, int64_t m, const do
     for (int i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
     std::vector<int64_t>& perm = h->perm[window];
     perm.assign(m, 0);
+    if (!h->perm_stale.empty()) h->perm_stale[window] = 1;
     {
         std::vector<int> cur(ptr.begin(), ptr.end() - 1);
         for (int64_t k = 0; k < m; ++k) perm[cur[ii[k]]++] = k;

@@ -5,6 +5,7 @@
 //                        replay), vba_iterate* (pipelined driver loop, host watch)
 //   vba_sharded_api.hip  observation-sharded mode (vba_sh_*)
 //   vba_cov.hip          per-pose marginal covariances (vba_covariance)
+//   vba_rel.hip          per-row leverages and w-tests (vba_reliability)
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -156,6 +157,13 @@ struct vba_context {
     float cov_ms = 0.f;
     bool cov_ran = false;
     bool sharded = false;                   // an observation-sharded call has run (vba_sh_*): no covariance query
+    // vba_reliability (vba_rel.hip): the two row arrays, the device copy of perm and the pose summary, allocated by the first query
+    void* d_rel = nullptr;
+    size_t rel_cap = 0;
+    std::vector<char> perm_stale;           // [W] once a reliability query has run: the device copy of perm[w] predates the last upload
+    hipEvent_t rel_ev = nullptr;
+    float rel_ms = 0.f;
+    bool rel_ran = false;
     // Pipelined driver loop (vba_iterate_resident, see iterate_pipelined): the call that was enqueued speculatively behind
     // the one that has just been returned, the chain it belongs to and what has been learnt about the caller's schedule
     struct Spec { bool valid = false; int iter = 0, init = 0; bool reg = false; int c = 0; } spec;
@@ -249,4 +257,16 @@ void watch_stop(vba_handle h);
 void watch_quiesce(vba_handle h);
 int vba_set_schedule_graph(vba_handle h, int on);      // (options of vba_set_option that live with the schedule)
 int vba_set_chain_profile(vba_handle h, int on);
+
+// ---- vba_cov.hip
+// The step the covariance and the reliability query share: the shadow front of a full-phase call and the selected inversion,
+// into the scratch of the query (see vba_cov.hip).
+struct CovQuery {
+    DevView V;                  // the shadow view: wraw, sc (maximum raw weight of parity V.par) and states are what the row pass reads
+    double* diag = nullptr;     // [W][n_max][81] Sigma_ii
+    double* sup = nullptr;      // [W][n_max][81] Sigma_i,i+1
+    unsigned* flags = nullptr;  // [W]
+};
+int cov_begin(vba_handle h, int iter, const char* who);
+int cov_build_invert(vba_handle h, int iter, int damped, CovQuery& q);
 #pragma GCC visibility pop

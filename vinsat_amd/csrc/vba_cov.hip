@@ -551,13 +551,23 @@ static int cov_scratch(vba_handle h) {
     return VBA_OK;
 }
 
-int vba_covariance(vba_handle h, int iter, int damped, double* diag, double* super, unsigned* flags) {
+// What every query checks first: the arguments, the handle's mode, a speculated call (dropped as a mismatched resident call drops
+// it), states in every window.  `who` names the entry point in the messages.
+int cov_begin(vba_handle h, int iter, const char* who) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (iter < 0) return fail(VBA_EINVAL, "iter must be >= 0");
-    if (h->sharded) return fail(VBA_ESTATE, "vba_covariance does not serve observation-sharded handles");
+    if (h->sharded) return fail(VBA_ESTATE, std::string(who) + " does not serve observation-sharded handles");
     if (int rc_settle = settle(h)) return rc_settle;        // a speculated call is dropped as a mismatched resident call drops it
     if (int rc = ready(h)) return rc;
     HIPCHK(hipSetDevice(h->device));
+    return VBA_OK;
+}
+
+// The shadow front and the selected inversion, enqueued on the handle's stream into the scratch of the query: the step
+// vba_covariance and vba_reliability (vba_rel.hip) share.  cov_ev[0] is recorded in front of it; the caller records its own end
+// event and synchronises.  q: the shadow view (its wraw, its window scalars with the maximum raw weight and its bands stay valid
+// until the next query) and the device results.
+int cov_build_invert(vba_handle h, int iter, int damped, CovQuery& q) {
     if (int rc = cov_scratch(h)) return rc;
     hipStream_t s = h->stream;
     if (!h->cov_ev[0]) {
@@ -569,7 +579,7 @@ int vba_covariance(vba_handle h, int iter, int damped, double* diag, double* sup
     // the front writes redirected into the scratch
     CallSpec c;
     c.iter = iter; c.initialize = 0; c.call = -1; c.par = h->par; c.emit = 0; c.carry = 0;
-    DevView V;
+    DevView& V = q.V;
     view_for_call(h, V, c);
     char* p = reinterpret_cast<char*>(h->d_cov);
     WinScalars* sc = carve<WinScalars>(p, W);
@@ -647,13 +657,25 @@ int vba_covariance(vba_handle h, int iter, int damped, double* diag, double* sup
                            d_flags);
     }
     HIPCHK(hipGetLastError());
+    q.diag = d_diag;
+    q.sup = d_sup;
+    q.flags = d_flags;
+    return VBA_OK;
+}
+
+int vba_covariance(vba_handle h, int iter, int damped, double* diag, double* super, unsigned* flags) {
+    if (int rc = cov_begin(h, iter, "vba_covariance")) return rc;
+    CovQuery q;
+    if (int rc = cov_build_invert(h, iter, damped, q)) return rc;
+    hipStream_t s = h->stream;
+    const size_t W = h->W, N = h->n_max;
     HIPCHK(hipEventRecord(h->cov_ev[1], s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipEventElapsedTime(&h->cov_ms, h->cov_ev[0], h->cov_ev[1]));
     h->cov_ran = true;
-    if (diag) HIPCHK(hipMemcpy(diag, d_diag, W * N * 81 * 8, hipMemcpyDeviceToHost));
-    if (super) HIPCHK(hipMemcpy(super, d_sup, W * N * 81 * 8, hipMemcpyDeviceToHost));
-    if (flags) HIPCHK(hipMemcpy(flags, d_flags, W * 4, hipMemcpyDeviceToHost));
+    if (diag) HIPCHK(hipMemcpy(diag, q.diag, W * N * 81 * 8, hipMemcpyDeviceToHost));
+    if (super) HIPCHK(hipMemcpy(super, q.sup, W * N * 81 * 8, hipMemcpyDeviceToHost));
+    if (flags) HIPCHK(hipMemcpy(flags, q.flags, W * 4, hipMemcpyDeviceToHost));
     return VBA_OK;
 }
 

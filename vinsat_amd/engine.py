@@ -298,6 +298,28 @@ class BAEngine:
         _lib.check(self.lib.vba_last_covariance_ms(self.h, byref(ms)), self.lib)
         return ms.value
 
+    def reliability(self, it, damped=False, pose_stats=False):
+        """``vba_reliability``: per observation row of every window, at the resident states, the leverage ``tr(P_k)`` and the
+        standardised residual (w-test) ``sqrt(w_k r_k^T (I - P_k)^-1 r_k)`` with ``P_k = w_k J_k S_i J_k^T`` and ``S_i`` the pose's
+        block of :meth:`covariance` (``include/vinsat_ba.h`` carries the definitions and the degenerate cases).
+
+        Returns ``(leverage [W, m_max], wtest [W, m_max], flags [W])`` in the input order of the rows -- with ``pose_stats`` also
+        ``[W, n_max, 3]``: per pose the sum of its leverages, its largest finite ``wtest`` and its count of rows with non-zero
+        weight, in front of ``flags``.  Rows beyond a window's ``m`` and poses beyond its ``n`` are NaN."""
+        W = self.windows
+        lev = np.full((W, self.m_max), np.nan)
+        wt = np.full((W, self.m_max), np.nan)
+        ps = np.full((W, self.n_max, 3), np.nan) if pose_stats else None
+        flags = np.empty(W, dtype=np.uint32)
+        _lib.check(self.lib.vba_reliability(self.h, int(it), int(bool(damped)), _p(lev), _p(wt), _p(ps) if ps is not None else None,
+                                            flags.ctypes.data_as(ctypes.POINTER(c_uint))), self.lib)
+        return (lev, wt, ps, flags) if pose_stats else (lev, wt, flags)
+
+    def last_reliability_ms(self):
+        ms = c_float()
+        _lib.check(self.lib.vba_last_reliability_ms(self.h, byref(ms)), self.lib)
+        return ms.value
+
     def debug(self, what, window=0):
         n, m = self.n[window], self.m[window]
         shapes = dict(est=(m, 2), weight=(m,), H=(n, 6, 6), b=(n, 6), Phi=(n, 6, 6), r_pred=(n - 1, 7), qgrad=(n, 3),

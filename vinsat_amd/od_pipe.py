@@ -401,7 +401,8 @@ class _Clock:
 
 
 def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, detections_file_name=None,
-                      ba=None, num_iters=NUM_ITERS, record=None, timing=None, run=None, device=0, covariances=None):
+                      ba=None, num_iters=NUM_ITERS, record=None, timing=None, run=None, device=0, covariances=None,
+                      reliability=None):
     """Drop-in for the reference's ``streaming_version`` (od_pipe.py:911-1062).
 
     ``ba`` defaults to the HIP-backed :func:`vinsat_amd.ba.BA`; tests may inject another
@@ -413,9 +414,14 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
     ``covariances`` (a list) receives, after every batch, the marginal covariance ``[9, 9]`` of the batch's last pose at its final
     states (:func:`vinsat_amd.ba.covariance`: [dp km, dtheta, dv km/s]) -- the pose whose error ``finish_patch`` records; it
     needs the default ``ba`` and leaves the estimates bit for bit as they are without it.
+    ``reliability`` (a list) receives, after every batch, ``dict(leverage, wtest)`` of that batch's rows in their input order
+    (:func:`vinsat_amd.ba.reliability`, ``[m]`` each) under the same two conditions.  Nothing is rejected on them here: the
+    outlier mask of the data preparation stays the ground-truth one of the reference.
     """
     if covariances is not None and ba is not None:
         raise ValueError("covariances needs the default (HIP) ba")
+    if reliability is not None and ba is not None:
+        raise ValueError("reliability needs the default (HIP) ba")
     ba_window = None
     rows_device = None
     if ba is None:
@@ -450,13 +456,19 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
             from .ba import covariance
             covariances.append(covariance()[0, -1].clone())
             t0 = clk("bookkeeping", t0)
+        if reliability is not None:
+            from .ba import reliability as _reliability
+            lev, wt = _reliability()
+            reliability.append(dict(leverage=lev[0].clone(), wtest=wt[0].clone()))
+            t0 = clk("bookkeeping", t0)
         run.finish_patch(states_t, vel_t)
     out = run.result()
     clk("bookkeeping", t0)
     return out
 
 
-def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=None, timing=None, threads=None, device=0, covariances=None):
+def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=None, timing=None, threads=None, device=0, covariances=None,
+                      reliability=None):
     """Many sequences at once -- the reference's outer loop over sequence files (od_pipe.py:1069-1077) turned into the batch
     dimension of ``BA``: round r runs batch r of EVERY sequence that still has one as the windows of ONE ragged handle
     (:func:`vinsat_amd.ba.BA_window` on lists: every kernel launch covers all of them), sequences that have ended drop out.
@@ -466,10 +478,14 @@ def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=Non
     ``record`` (a list) receives ``dict(round, sequence, states, lamda)`` after every round; ``timing`` (a dict) the wall time
     by phase (:class:`_Clock`).  ``covariances`` (a list) receives ``dict(round, sequence, cov)`` after every round: ``cov`` the
     marginal covariance ``[9, 9]`` of the last pose of that sequence's batch (:func:`vinsat_amd.ba.covariance`); it needs the
-    default ``ba_window`` and changes no result.
+    default ``ba_window`` and changes no result.  ``reliability`` (a list) receives ``dict(round, sequence, leverage, wtest)`` after
+    every round: the values of that sequence's batch rows in their input order (:func:`vinsat_amd.ba.reliability`), under the same
+    conditions.
     """
     if covariances is not None and ba_window is not None:
         raise ValueError("covariances needs the default (HIP) ba_window")
+    if reliability is not None and ba_window is not None:
+        raise ValueError("reliability needs the default (HIP) ba_window")
     rows_device = None
     if ba_window is None:
         rows_device = device            # (the HIP BA is in use: the per-row preparation runs on its device as well)
@@ -508,6 +524,14 @@ def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=Non
             cov = cov if isinstance(cov, list) else [cov]
             for (k, _, _), c in zip(live, cov):
                 covariances.append(dict(round=rnd, sequence=k, cov=c[0, -1].clone()))
+            t0 = clk("bookkeeping", t0)
+        if reliability is not None:
+            from .ba import reliability as _reliability
+            lev, wt = _reliability()
+            if not isinstance(lev, list):
+                lev, wt = [lev], [wt]
+            for (k, _, _), a, b in zip(live, lev, wt):
+                reliability.append(dict(round=rnd, sequence=k, leverage=a[0].clone(), wtest=b[0].clone()))
             t0 = clk("bookkeeping", t0)
         for (k, r, p), s_new, l_new in zip(live, st, lam):
             if record is not None:
