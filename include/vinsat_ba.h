@@ -346,6 +346,61 @@ int vba_reliability(vba_handle h, int iter, int damped, double* leverage, double
 /* HIP-event time of the last vba_reliability on the handle's stream (front + inversion + row pass), milliseconds. */
 int vba_last_reliability_ms(vba_handle h, float* ms);
 
+/* ---- outlier power: per row, how large an error in it could pass the w-test unnoticed (minimal detectable bias), how far such an
+ * error would move the pose (external reliability) and how far the row itself moves it (deletion influence); per pose and per
+ * window, the weighted residual sum, the redundancy and the a-posteriori variance factor of the fit.  At the RESIDENT states, for a
+ * full-phase call BA(iter), with the system of vba_covariance(h, iter, damped, ...): the same A^, the same damping and
+ * symmetrisation rules, Sigma = A^^-1.  J_k, r_k, w_k, S_i and P_k are those of vba_reliability, for observation row k of pose
+ * i = ii[k]; further
+ *   R_k        I - P_k (2x2); only its symmetric part is formed.  R_k / w_k is the covariance of the row's residual;
+ *   B_k [6,2]  w_k S_i J_k^T: the change of the pose's [dp, dtheta] per pixel of error in the row; B_p its rows 0..2, B_t rows 3..5;
+ *   ncp > 0    the non-centrality parameter of the test, the caller's choice (17.075 for a 0.1 % test of 80 % power);
+ *   crit > 0   the critical value wtest is counted against, the caller's choice (+inf counts nothing);
+ *   mdb      [W][m_max]  sqrt(ncp / (w_k mu_min(R_k))), pixels: the minimal detectable bias along the direction the test sees
+ *                        worst.  mu_min, the smaller eigenvalue of the symmetric 2x2, is (tr - sqrt((a - d)^2 + 4 b^2)) / 2:
+ *                        continuous in its inputs, no tie rule;
+ *   ext_pos  [W][m_max]  sqrt(ncp / w_k  mu_max(B_p^T B_p, R_k)), km: the largest displacement of the pose's position that a bias
+ *                        at the detection limit causes.  mu_max(M, R) is the larger root of det(M - mu R) = 0, a quadratic in
+ *                        closed form (csrc/vba_power_math.h); no eigenvector of R_k is formed, so the value stays continuous
+ *                        where the eigenvalues of R_k coincide and no row is excluded;
+ *   ext_att  [W][m_max]  2 sqrt(ncp / w_k  mu_max(B_t^T B_t, R_k)), radians by the 2 |dtheta| convention of vba_covariance;
+ *   del_pos  [W][m_max]  | B_p R_k^-1 r_k |, km: under the linearised model, the distance the pose's position moves if row k is
+ *                        removed;
+ *   pose_fit [W][n_max][4]  per pose: Omega_i = sum of w_k |r_k|^2 over its rows; the sum of its leverages (the bits of
+ *                        vba_reliability's pose_stats[..., 0]); the largest finite ext_pos of its rows; the count of its rows
+ *                        with wtest > crit.  Poses without rows get 0, 0, 0, 0;
+ *   fit      [W][8]      per window: Omega = sum of Omega_i; m_eff, the number of rows with w_k > 0; t, the sum of the
+ *                        leverages; rho = 2 m_eff - t, the redundancy; s0sq = Omega / rho (NaN if rho <= 0); the largest finite
+ *                        wtest (the maximum of vba_reliability's wtest, bit for bit); the count of rows with wtest > crit; the
+ *                        largest finite ext_pos;
+ *   flags [W]  the flags of the covariance step (see vba_covariance).
+ * What s0sq is and is not.  It is the a-posteriori variance factor of the OBSERVATION class -- the 2 m_eff reprojection residuals
+ * against the parameters they determine --, in the units of the normalised weights (w_raw / w_max) conf: with s0 = sqrt(s0sq),
+ * s0^2 Sigma is the covariance vba_covariance leaves unscaled, s0 scales the sigmas, mdb and ext_* linearly and wtest inversely
+ * (wtest / s0 is what compares with a critical value of the standard normal / chi distribution).  It is NOT a variance factor
+ * of the whole system: the orbit and attitude factors carry weights of 1e4 .. 1e6 (times 100 on the velocities), which makes
+ * them constraints in all but name; the redundancy of such an edge is a difference of two numbers equal to rounding in a system
+ * of condition ~1e11, so no variance component of those classes is computed.  They enter every number here through Sigma only.
+ * The row arrays are in the INPUT order of the rows.  Degenerate rows are flagged in the value: w_k == 0 gives mdb = +inf,
+ * ext_pos = ext_att = del_pos = 0; det R_k <= 0 or mu_min(R_k) <= 0 gives NaN in all four; a window flagged VBA_FLAG_ZERO_PIVOT /
+ * VBA_FLAG_NONFINITE has no Sigma: NaN in all four for every row of it (those of weight zero included); its Omega and m_eff
+ * stand, t, rho and s0sq are NaN if a row of it has weight.
+ * Any output may be NULL, in every combination; rows beyond a window's m and poses beyond its n are left untouched.  VBA_EINVAL
+ * if ncp is not positive and finite or crit is not positive.  Precision: as vba_reliability (J_k in fp64 whatever
+ * VBA_OPT_JACOBIAN_F32 says).
+ * Algorithm: the shadow front and the selected inversion of vba_covariance into the scratch of the query, one streaming pass over
+ * the rows with the mapping and the leverage / w-test arithmetic of vba_reliability, and one wavefront per window for the totals
+ * (csrc/vba_power.hip): no atomics, equal settings give equal bits, a window has the same bits alone and in a batch.  The
+ * promises are those of vba_covariance: the query changes nothing (states, lamda, flags, carried keys, schedule graphs, long-gap
+ * pool), drops a speculated pipelined call as a mismatched resident call does, returns VBA_ESTATE before every window has states
+ * and on observation-sharded handles, and is synchronous.  Scratch beyond the reliability query's (which is allocated too: its
+ * index per row is read) is allocated on the first query: four doubles per observation row and window, whichever outputs are asked
+ * for; VBA_ENOMEM if that fails.  Only the non-NULL outputs are copied to the host. */
+int vba_outlier_power(vba_handle h, int iter, int damped, double ncp, double crit, double* mdb, double* ext_pos, double* ext_att,
+                      double* del_pos, double* pose_fit, double* fit, unsigned* flags);
+/* HIP-event time of the last vba_outlier_power on the handle's stream (front + inversion + row pass + window totals), milliseconds. */
+int vba_last_outlier_power_ms(vba_handle h, float* ms);
+
 /* Timing of the last vba_step measured with HIP events on the handle's stream, milliseconds. */
 int vba_last_step_ms(vba_handle h, float* ms);
 

@@ -749,6 +749,77 @@ def reliability(iter=None, damped=False):
 reliability.last = {}
 
 
+FIT_FIELDS = ("omega", "m_eff", "leverage_sum", "dof", "s0sq", "wtest_max", "n_flagged", "ext_pos_max")
+
+
+def outlier_power(iter=None, damped=False, ncp=17.075, crit=None):
+    """Outlier power at the states the last :func:`BA` / :func:`BA_reg` / :func:`BA_window` call returned
+    (``vba_outlier_power``, ``include/vinsat_ba.h``).  Per row, in the order the rows were passed in: ``mdb``, the minimal
+    detectable bias in pixels (the error in the row that the w-test of :func:`reliability` finds with the power ``ncp`` stands
+    for -- 17.075: a 0.1 % test, 80 % power -- along the direction it sees worst); ``ext_pos`` (km) and ``ext_att`` (rad), the
+    largest displacement of the pose such an undetected error causes; ``del_pos`` (km), how far the pose's position moves if the
+    row is removed.  ``iter``, ``damped`` and the prior as in :func:`covariance`.  ``crit``: the critical value rows are
+    counted against (``None``: count nothing).  A row of weight zero gives ``inf, 0, 0, 0``, a degenerate row or a window
+    without a covariance NaN.
+
+    Returns ``(mdb, ext_pos, ext_att, del_pos, fit)``; the arrays are shaped as :func:`reliability`'s, ``fit`` is one record per
+    window (a list for a batch) with the fields ``omega`` (sum of ``w |r|^2``), ``m_eff`` (rows of non-zero weight),
+    ``leverage_sum``, ``dof`` (the redundancy ``2 m_eff - leverage_sum``), ``s0sq = omega / dof`` and ``s0 = sqrt(s0sq)``,
+    ``wtest_max``, ``n_flagged`` (rows with ``wtest > crit``), ``ext_pos_max`` and ``flags``.  ``s0sq`` is the a-posteriori
+    variance factor of the observation class in the units of the normalised weights: ``s0`` scales the sigmas
+    (:func:`scaled_sigmas`), ``mdb`` and ``ext_*`` linearly and ``wtest`` inversely; the orbit and attitude factors enter through
+    the covariance only.  ``outlier_power.last["pose_fit"]``: per pose ``[.., n, 4]`` the sum of ``w |r|^2``, the sum of
+    leverages, the largest finite ``ext_pos``, the rows with ``wtest > crit``.  The device states, damping and the bits of the
+    following calls are not changed."""
+    import collections
+    import torch
+    q = _cache.get("last_query")
+    eng = _cache.get(q["eng"]) if q is not None else None
+    if eng is None or not getattr(eng, "h", None):
+        raise RuntimeError("outlier_power() needs a preceding BA / BA_reg / BA_window call")
+    it = q["iter"] if iter is None else int(iter)
+    if q["reg"]:
+        eng.set_prior(True)
+    try:
+        *rows, pf, fit, flags = eng.outlier_power(it, damped=damped, ncp=ncp, crit=crit)
+    finally:
+        if q["reg"]:
+            eng.set_prior(False)
+    ns, form = q["ns"], q["form"]
+    ms = [int(eng.m[b]) for b in range(len(ns))]
+
+    def shaped(a, counts):
+        if form == "single":
+            return torch.from_numpy(np.ascontiguousarray(a[:1, :counts[0]]))
+        if form == "dense":
+            return torch.from_numpy(np.ascontiguousarray(a[:len(counts), :counts[0]]))
+        return [torch.from_numpy(np.ascontiguousarray(a[b:b + 1, :c])) for b, c in enumerate(counts)]
+
+    Fit = collections.namedtuple("Fit", FIT_FIELDS + ("s0", "flags"))
+    recs = [Fit(*[float(x) for x in fit[b]], s0=float(np.sqrt(fit[b, 4])) if fit[b, 4] >= 0 else float("nan"), flags=int(flags[b]))
+            for b in range(len(ns))]
+    outlier_power.last = dict(pose_fit=shaped(pf, ns))
+    return (*[shaped(a, ms) for a in rows], recs[0] if form == "single" else recs)
+
+
+outlier_power.last = {}
+
+
+def scaled_sigmas(cov, fit):
+    """:func:`pose_sigmas` of ``cov`` times ``s0`` of ``fit`` (:func:`outlier_power`): 1-sigma values in km, km/s and rad under the
+    a-posteriori variance factor of the observation class.  ``fit``: one record, or a list of records -- one per window of a
+    batch (``cov`` a list, or a dense ``[B, n, 9, 9]``)."""
+    if isinstance(fit, (list, tuple)) and not hasattr(fit, "s0"):
+        if isinstance(cov, (list, tuple)):
+            return [scaled_sigmas(c, f) for c, f in zip(cov, fit)]
+        per = [scaled_sigmas(cov[b:b + 1], f) for b, f in enumerate(fit)]
+        if isinstance(cov, np.ndarray):
+            return tuple(np.concatenate([p[k] for p in per]) for k in range(3))
+        import torch
+        return tuple(torch.cat([p[k] for p in per]) for k in range(3))
+    return tuple(x * fit.s0 for x in pose_sigmas(cov))
+
+
 def pose_sigmas(cov):
     """1-sigma per pose from marginal blocks ``cov [..., n, 9, 9]`` (:func:`covariance`): ``(position [..., n, 3] km,
     velocity [..., n, 3] km/s, attitude [..., n, 3] rad)``.  The step's ``dtheta`` linearises a rotation of angle ``2 dtheta``,

@@ -405,6 +405,8 @@ int vba_destroy(vba_handle h) {
     if (h->d_cov) hipFree(h->d_cov);
     if (h->d_rel) hipFree(h->d_rel);
     if (h->rel_ev) hipEventDestroy(h->rel_ev);
+    if (h->d_pow) hipFree(h->d_pow);
+    if (h->pow_ev) hipEventDestroy(h->pow_ev);
     for (hipEvent_t e : h->cov_ev) if (e) hipEventDestroy(e);
     if (h->arena.base) hipFree(h->arena.base);
     delete h;

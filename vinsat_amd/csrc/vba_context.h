@@ -6,6 +6,7 @@
 //   vba_sharded_api.hip  observation-sharded mode (vba_sh_*)
 //   vba_cov.hip          per-pose marginal covariances (vba_covariance)
 //   vba_rel.hip          per-row leverages and w-tests (vba_reliability)
+//   vba_power.hip        per-row detectable biases and influences, the fit's variance factor (vba_outlier_power)
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -164,6 +165,12 @@ struct vba_context {
     hipEvent_t rel_ev = nullptr;
     float rel_ms = 0.f;
     bool rel_ran = false;
+    // vba_outlier_power (vba_power.hip): four row arrays, the pose and window summaries, allocated by the first query
+    void* d_pow = nullptr;
+    size_t pow_cap = 0;
+    hipEvent_t pow_ev = nullptr;
+    float pow_ms = 0.f;
+    bool pow_ran = false;
     // Pipelined driver loop (vba_iterate_resident, see iterate_pipelined): the call that was enqueued speculatively behind
     // the one that has just been returned, the chain it belongs to and what has been learnt about the caller's schedule
     struct Spec { bool valid = false; int iter = 0, init = 0; bool reg = false; int c = 0; } spec;
@@ -269,4 +276,12 @@ struct CovQuery {
 };
 int cov_begin(vba_handle h, int iter, const char* who);
 int cov_build_invert(vba_handle h, int iter, int damped, CovQuery& q);
+
+// ---- vba_rel.hip
+// What the row passes behind the covariance step share on the host: the device copy of the upload's permutation (sorted position ->
+// input row, [W][m_max], part of the reliability scratch, uploaded for the windows whose rows changed), and the copy of a
+// per-window result to the host (`used[w] * per` doubles of every window's `stride`; the rest stays as the caller left it).
+size_t rel_round(size_t b);
+int rel_device_perm(vba_handle h, const int** d_perm);
+int rel_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per);
 #pragma GCC visibility pop

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void k_reliability(DevView V, const double* __
 
 // scratch of the row pass: lev, wt [W][m_max] doubles, perm [W][m_max] ints, pstat [W][n_max][3] doubles -- 20 bytes per row and
 // window (W = 4096 windows of 50 000 rows: 1.6 GB per row array, 4.1 GB in all)
-static size_t rel_round(size_t b) { return (b + 255) & ~size_t(255); }
+size_t rel_round(size_t b) { return (b + 255) & ~size_t(255); }
 
 static int rel_scratch(vba_handle h) {
     const size_t W = h->W, N = h->n_max, M = h->m_max;
@@ -160,7 +160,7 @@ static int rel_scratch(vba_handle h) {
 }
 
 // per-window results: rows beyond a window's count stay as the caller left them
-static int rel_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per) {
+int rel_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per) {
     bool full = true;
     for (size_t w = 0; w < W; ++w) full = full && (size_t)used[w] * per == stride;
     if (full) {
@@ -183,6 +183,31 @@ static int rel_copy_out(double* out, const double* dev, size_t W, size_t stride,
     return VBA_OK;
 }
 
+// the input position of every sorted row, for the windows whose rows were uploaded since the last query of either row pass
+// (one copy over the range of windows that holds them)
+static int rel_upload_perm(vba_handle h, int* d_perm) {
+    const size_t W = h->W, M = h->m_max;
+    size_t lo = W, hi = 0;
+    for (size_t w = 0; w < W; ++w)
+        if (h->perm_stale[w]) { lo = std::min(lo, w); hi = w + 1; }
+    if (lo < hi) {
+        std::vector<int> tmp((hi - lo) * M, 0);
+        for (size_t w = lo; w < hi; ++w) std::copy(h->perm[w].begin(), h->perm[w].end(), tmp.begin() + (w - lo) * M);
+        HIPCHK(hipMemcpy(d_perm + lo * M, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
+        std::fill(h->perm_stale.begin(), h->perm_stale.end(), 0);
+    }
+    return VBA_OK;
+}
+
+// The device copy of the permutation, brought up to date: what vba_outlier_power (vba_power.hip) takes from this scratch.
+int rel_device_perm(vba_handle h, const int** d_perm) {
+    if (int rc = rel_scratch(h)) return rc;
+    int* p = reinterpret_cast<int*>(reinterpret_cast<char*>(h->d_rel) + 2 * rel_round((size_t)h->W * h->m_max * 8));
+    if (int rc = rel_upload_perm(h, p)) return rc;
+    *d_perm = p;
+    return VBA_OK;
+}
+
 int vba_reliability(vba_handle h, int iter, int damped, double* leverage, double* wtest, double* pose_stats, unsigned* flags) {
     if (int rc = cov_begin(h, iter, "vba_reliability")) return rc;
     if (int rc = rel_scratch(h)) return rc;
@@ -194,19 +219,7 @@ int vba_reliability(vba_handle h, int iter, int damped, double* leverage, double
     int* d_perm = reinterpret_cast<int*>(p); p += rel_round(W * M * 4);
     double* d_pstat = reinterpret_cast<double*>(p);
     hipStream_t s = h->stream;
-    // the input position of every sorted row, for the windows whose rows were uploaded since the last query
-    // (one copy over the range of windows that holds them)
-    {
-        size_t lo = W, hi = 0;
-        for (size_t w = 0; w < W; ++w)
-            if (h->perm_stale[w]) { lo = std::min(lo, w); hi = w + 1; }
-        if (lo < hi) {
-            std::vector<int> tmp((hi - lo) * M, 0);
-            for (size_t w = lo; w < hi; ++w) std::copy(h->perm[w].begin(), h->perm[w].end(), tmp.begin() + (w - lo) * M);
-            HIPCHK(hipMemcpy(d_perm + lo * M, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
-            std::fill(h->perm_stale.begin(), h->perm_stale.end(), 0);
-        }
-    }
+    if (int rc = rel_upload_perm(h, d_perm)) return rc;
     CovQuery q;
     if (int rc = cov_build_invert(h, iter, damped, q)) return rc;
     HIPCHK(hipMemsetAsync(d_pstat, 0, W * N * 3 * 8, s));       // (blocks beyond a window's poses do not run)

@@ -320,6 +320,32 @@ class BAEngine:
         _lib.check(self.lib.vba_last_reliability_ms(self.h, byref(ms)), self.lib)
         return ms.value
 
+    def outlier_power(self, it, damped=False, ncp=17.075, crit=None):
+        """``vba_outlier_power``: per observation row of every window, at the resident states, the minimal detectable bias
+        ``mdb`` (pixels), the external reliability ``ext_pos`` (km) and ``ext_att`` (rad) and the deletion influence ``del_pos``
+        (km); per pose ``pose_fit [W, n_max, 4]`` (sum of ``w |r|^2``, sum of leverages, largest finite ``ext_pos``, rows with
+        ``wtest > crit``); per window ``fit [W, 8]`` (Omega, m_eff, t, rho, s0sq, largest finite wtest, rows with
+        ``wtest > crit``, largest finite ``ext_pos``).  ``include/vinsat_ba.h`` carries the definitions and the degenerate
+        cases.  ``ncp``: the non-centrality parameter of the test; ``crit``: the critical value rows are counted against
+        (``None``: count nothing).
+
+        Returns ``(mdb, ext_pos, ext_att, del_pos, pose_fit, fit, flags)``, the row arrays ``[W, m_max]`` in the input order of
+        the rows.  Rows beyond a window's ``m`` and poses beyond its ``n`` are NaN."""
+        W = self.windows
+        rows = [np.full((W, self.m_max), np.nan) for _ in range(4)]
+        pf = np.full((W, self.n_max, 4), np.nan)
+        fit = np.empty((W, 8))
+        flags = np.empty(W, dtype=np.uint32)
+        _lib.check(self.lib.vba_outlier_power(self.h, int(it), int(bool(damped)), float(ncp), np.inf if crit is None else float(crit),
+                                              *[_p(a) for a in rows], _p(pf), _p(fit),
+                                              flags.ctypes.data_as(ctypes.POINTER(c_uint))), self.lib)
+        return (*rows, pf, fit, flags)
+
+    def last_outlier_power_ms(self):
+        ms = c_float()
+        _lib.check(self.lib.vba_last_outlier_power_ms(self.h, byref(ms)), self.lib)
+        return ms.value
+
     def debug(self, what, window=0):
         n, m = self.n[window], self.m[window]
         shapes = dict(est=(m, 2), weight=(m,), H=(n, 6, 6), b=(n, 6), Phi=(n, 6, 6), r_pred=(n - 1, 7), qgrad=(n, 3),
