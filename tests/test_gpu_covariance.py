@@ -13,37 +13,11 @@ import pytest
 
 import cov_oracle as C
 from oracle import ba_oracle as O
+from query_windows import INITS, _engine, _scheduled, _win
 
 pytestmark = pytest.mark.gpu
 
 ZERO_PIVOT, INDEFINITE = 4, 8
-
-
-def _win(cfg, seed=0):
-    from vinsat_amd import od_pipe, synth
-    det, orb = synth.make_sequence(cfg, seed=seed)
-    return od_pipe.prepare_window(det, orb)
-
-
-def _engine(win, mode=-1, windows=1, n_max=None, m_max=None):
-    from vinsat_amd.engine import BAEngine
-    n = win.states_gt.shape[0]
-    eng = BAEngine(n_max or n, m_max or win.ii.size, windows=windows, mode=mode)
-    for w in range(windows):
-        eng.upload_observations(win.landmarks_xyz, win.landmarks_uv, win.confidences, win.ii, n, window=w)
-        eng.upload_window(win.intrinsics, win.cumrot_last, win.time_idx, window=w)
-    return eng
-
-
-INITS = [it < 10 for it in range(20)]
-
-
-def _scheduled(win, eng, calls=20):
-    from vinsat_amd import od_pipe
-    eng.set_states(od_pipe.initial_guess(win), 1e-4)
-    eng.run_schedule(list(range(calls)), INITS[:calls])
-    st, lam, _, _, _ = eng.get_states()
-    return st, lam
 
 
 def _oracle_bands(win, st, lam, it=19, **kw):

@@ -13,38 +13,14 @@ import numpy as np
 import pytest
 
 import power_oracle as PO
-import random_windows
+from query_windows import INITS, SMALL_LAMDA, _ba_args, _batch_engine, _engine, _scheduled, _small_windows, _win
 
 pytestmark = pytest.mark.gpu
 
 ZERO_PIVOT, NONFINITE, INDEFINITE = 4, 2, 8
-INITS = [it < 10 for it in range(20)]
 BAR = 1e-8
 ROWS = ("mdb", "ext_pos", "ext_att", "del_pos")
 CRIT = 2.0
-
-
-def _win(cfg, seed=0):
-    from vinsat_amd import od_pipe, synth
-    det, orb = synth.make_sequence(cfg, seed=seed)
-    return od_pipe.prepare_window(det, orb)
-
-
-def _engine(win, **kw):
-    from vinsat_amd.engine import BAEngine
-    n = win.states_gt.shape[0]
-    eng = BAEngine(n, win.ii.size, **kw)
-    eng.upload_observations(win.landmarks_xyz, win.landmarks_uv, win.confidences, win.ii, n)
-    eng.upload_window(win.intrinsics, win.cumrot_last, win.time_idx)
-    return eng
-
-
-def _scheduled(win, eng, calls=20):
-    from vinsat_amd import od_pipe
-    eng.set_states(od_pipe.initial_guess(win), 1e-4)
-    eng.run_schedule(list(range(calls)), INITS[:calls])
-    st, lam, _, _, _ = eng.get_states()
-    return st, lam
 
 
 def _errors(got, ref, m, n):
@@ -160,66 +136,6 @@ def test_consistent_with_the_reliability_query_of_the_same_handle():
 
 
 # ------------------------------------------------------------------------------------------------ smallest shapes
-class _Small:
-    """A window cut from one of tests/random_windows.py: its first ``n`` poses, and of each pose the first ``rows[i]`` rows
-    (poses not named keep theirs)."""
-
-    def __init__(self, seed, n, rows):
-        win = random_windows.make(seed)[0]
-        assert win.time_idx.size >= n
-        keep = []
-        for i in range(n):
-            k = np.nonzero(win.ii == i)[0]
-            want = rows.get(i, k.size)
-            assert k.size >= want, (seed, i, k.size)
-            keep.append(k[:want])
-        keep = np.concatenate(keep)
-        order = np.random.default_rng(seed).permutation(keep.size)       # (not pose sorted)
-        keep = keep[order]
-        self.landmarks_xyz, self.landmarks_uv = win.landmarks_xyz[keep], win.landmarks_uv[keep]
-        self.confidences, self.ii = win.confidences[keep], win.ii[keep]
-        self.intrinsics, self.cumrot_last, self.time_idx = win.intrinsics[:n], win.cumrot_last[:n], win.time_idx[:n]
-        self.states0 = win.states_gt[:n].copy()
-        self.n, self.m = n, keep.size
-
-
-# The damping of the small windows' query.  Three rows on one pose of two determine that pose's six coordinates and no more: the
-# redundancy the rows lack comes from the damping, and so does the conditioning -- the dynamics factors weigh 1e4 .. 1e6 against
-# it.  At 100 the dense references of the 2-pose window differ (LU against Cholesky, at these states) by 2.4e-10 in del_pos and
-# 2.3e-10 in ext_pos, less elsewhere (17 poses: 2.9e-11), so the 1e-8 bar holds ten times the spread; at 1 they differ by 9.6e-8.
-SMALL_LAMDA = 100.0
-
-
-def _small_windows():
-    seed = next(s for s in range(200) if _fits(s))
-    two = _Small(seed, 2, {0: 3, 1: 0})
-    many = _Small(seed, 17, {0: 1, 1: 16, 2: 17, 3: 33})
-    dead = _Small(seed, 17, {})
-    dead.confidences = np.zeros_like(dead.confidences)
-    return two, many, dead
-
-
-def _fits(seed):
-    win = random_windows.make(seed)[0]
-    if win.time_idx.size < 17:
-        return False
-    c = np.bincount(win.ii, minlength=17)
-    return c[0] >= 3 and c[1] >= 16 and c[2] >= 17 and c[3] >= 33
-
-
-def _batch_engine(wins, chunk=None, sizes=None, **kw):
-    from vinsat_amd.engine import BAEngine
-    n_max, m_max = sizes or (max(w.n for w in wins), max(w.m for w in wins))
-    eng = BAEngine(n_max, m_max, windows=len(wins), **kw)
-    if chunk is not None:
-        eng.set_solver(chunk)
-    for k, w in enumerate(wins):
-        eng.upload_observations(w.landmarks_xyz, w.landmarks_uv, w.confidences, w.ii, w.n, window=k)
-        eng.upload_window(w.intrinsics, w.cumrot_last, w.time_idx, window=k)
-        eng.set_states(w.states0, SMALL_LAMDA, window=k)
-    return eng
-
-
 def test_smallest_shapes_alone_in_a_batch_and_on_both_solver_paths():
     """A 2-pose window with 3 rows on pose 0 and none on pose 1; 17 poses (two blocks of the grid) with 1, 16, 17 and 33 rows on
     poses 0..3; a window with every confidence zero.  Against the oracle with the damping on (undamped, the three rows of the
@@ -289,12 +205,6 @@ def test_query_changes_nothing_in_a_chained_schedule():
     assert np.array_equal(sa, sb) and la == lb and fa == fb
     a.close()
     b.close()
-
-
-def _ba_args(w):
-    imu = np.zeros((1, w.states_gt.shape[0], 2, 10))
-    imu[0, :, -1, 6:10] = w.cumrot_last
-    return imu, w.landmarks_uv[None], w.landmarks_xyz[None], w.ii, w.time_idx, w.intrinsics[None], w.confidences
 
 
 def test_pipelined_BA_loop_and_BA_window_keep_their_bits():

@@ -12,35 +12,12 @@ import numpy as np
 import pytest
 
 import rel_oracle as R
+from query_windows import INITS, _ba_args, _engine, _scheduled, _win
 
 pytestmark = pytest.mark.gpu
 
 ZERO_PIVOT, NONFINITE, INDEFINITE = 4, 2, 8
-INITS = [it < 10 for it in range(20)]
 BAR = 1e-8
-
-
-def _win(cfg, seed=0):
-    from vinsat_amd import od_pipe, synth
-    det, orb = synth.make_sequence(cfg, seed=seed)
-    return od_pipe.prepare_window(det, orb)
-
-
-def _engine(win, **kw):
-    from vinsat_amd.engine import BAEngine
-    n = win.states_gt.shape[0]
-    eng = BAEngine(n, win.ii.size, **kw)
-    eng.upload_observations(win.landmarks_xyz, win.landmarks_uv, win.confidences, win.ii, n)
-    eng.upload_window(win.intrinsics, win.cumrot_last, win.time_idx)
-    return eng
-
-
-def _scheduled(win, eng, calls=20):
-    from vinsat_amd import od_pipe
-    eng.set_states(od_pipe.initial_guess(win), 1e-4)
-    eng.run_schedule(list(range(calls)), INITS[:calls])
-    st, lam, _, _, _ = eng.get_states()
-    return st, lam
 
 
 def _assert_no_degenerate_row(ref, dbg):
@@ -178,12 +155,6 @@ def test_pipelined_BA_loop_keeps_its_bits():
     got = loop(9)
     assert torch.equal(ref[0], got[0]) and ref[1] == got[1]
     ba.release()
-
-
-def _ba_args(w):
-    imu = np.zeros((1, w.states_gt.shape[0], 2, 10))
-    imu[0, :, -1, 6:10] = w.cumrot_last
-    return imu, w.landmarks_uv[None], w.landmarks_xyz[None], w.ii, w.time_idx, w.intrinsics[None], w.confidences
 
 
 def test_window_alone_and_as_window_3_of_a_ragged_batch_at_pinned_settings():

@@ -660,6 +660,37 @@ BA_window.last = {}
 
 
 # ------------------------------------------------------------------------------------------------ uncertainty
+def _query(name, call, iter):
+    """``call(eng, it)`` on the engine of the last BA / BA_reg / BA_window call, with the prior on iff that call was ``BA_reg``.
+    Returns ``(eng, result, ns, form)``; ``iter`` defaults to that call's."""
+    q = _cache.get("last_query")
+    eng = _cache.get(q["eng"]) if q is not None else None
+    if eng is None or not getattr(eng, "h", None):
+        raise RuntimeError(f"{name}() needs a preceding BA / BA_reg / BA_window call")
+    it = q["iter"] if iter is None else int(iter)
+    if q["reg"]:
+        eng.set_prior(True)
+    try:
+        res = call(eng, it)
+    finally:
+        if q["reg"]:
+            eng.set_prior(False)
+    return eng, res, q["ns"], q["form"]
+
+
+def _shaped(a, counts, form):
+    """The used part of a per-window array ``[W, max count, ...]`` in the form of the last call: ``[1, count, ...]``, a dense
+    ``[B, count, ...]`` or a list of ``[1, count_b, ...]`` (fp64 torch tensors); None stays None."""
+    import torch
+    if a is None:
+        return None
+    if form == "single":
+        return torch.from_numpy(np.ascontiguousarray(a[:1, :counts[0]]))
+    if form == "dense":
+        return torch.from_numpy(np.ascontiguousarray(a[:len(counts), :counts[0]]))
+    return [torch.from_numpy(np.ascontiguousarray(a[b:b + 1, :c])) for b, c in enumerate(counts)]
+
+
 def covariance(iter=None, damped=False, super_diagonal=False):
     """Marginal covariances of the poses at the states the last :func:`BA` / :func:`BA_reg` / :func:`BA_window` call returned
     (``vba_covariance``, ``include/vinsat_ba.h``): the diagonal blocks ``Sigma_ii`` -- and with ``super_diagonal`` the blocks
@@ -673,34 +704,11 @@ def covariance(iter=None, damped=False, super_diagonal=False):
     ``[1, n_b, 9, 9]`` for a ragged one (fp64 torch tensors).  ``covariance.last["flags"]``: the ``VBA_FLAG_*`` bits per window
     (4: singular -- that window's blocks are NaN; 8: indefinite -- no covariance).  The device states, damping and the bits of
     the following calls are not changed."""
-    import torch
-    q = _cache.get("last_query")
-    eng = _cache.get(q["eng"]) if q is not None else None
-    if eng is None or not getattr(eng, "h", None):
-        raise RuntimeError("covariance() needs a preceding BA / BA_reg / BA_window call")
-    it = q["iter"] if iter is None else int(iter)
-    if q["reg"]:
-        eng.set_prior(True)
-    try:
-        res = eng.covariance(it, damped=damped, super_diagonal=super_diagonal)
-    finally:
-        if q["reg"]:
-            eng.set_prior(False)
+    _, res, ns, form = _query("covariance", lambda eng, it: eng.covariance(it, damped=damped, super_diagonal=super_diagonal), iter)
     diag, sup, flags = res if super_diagonal else (res[0], None, res[1])
-    ns, form = q["ns"], q["form"]
-
-    def shaped(a):
-        if a is None:
-            return None
-        if form == "single":
-            return torch.from_numpy(np.ascontiguousarray(a[:1, :ns[0]]))
-        if form == "dense":
-            return torch.from_numpy(np.ascontiguousarray(a[:len(ns), :ns[0]]))
-        return [torch.from_numpy(np.ascontiguousarray(a[b:b + 1, :n])) for b, n in enumerate(ns)]
-
     fl = [int(x) for x in flags[:len(ns)]]
     covariance.last = dict(flags=fl[0] if form == "single" else fl)
-    return (shaped(diag), shaped(sup)) if super_diagonal else shaped(diag)
+    return (_shaped(diag, ns, form), _shaped(sup, ns, form)) if super_diagonal else _shaped(diag, ns, form)
 
 
 covariance.last = {}
@@ -718,32 +726,11 @@ def reliability(iter=None, damped=False):
     one (fp64).  ``reliability.last["flags"]``: the ``VBA_FLAG_*`` bits per window as ``covariance.last``; ``["pose_stats"]``: per
     pose the sum of its leverages, its largest finite ``wtest``, its count of rows with non-zero weight (``[1, n, 3]`` / ``[B, n, 3]``
     / a list).  The device states, damping and the bits of the following calls are not changed."""
-    import torch
-    q = _cache.get("last_query")
-    eng = _cache.get(q["eng"]) if q is not None else None
-    if eng is None or not getattr(eng, "h", None):
-        raise RuntimeError("reliability() needs a preceding BA / BA_reg / BA_window call")
-    it = q["iter"] if iter is None else int(iter)
-    if q["reg"]:
-        eng.set_prior(True)
-    try:
-        lev, wt, ps, flags = eng.reliability(it, damped=damped, pose_stats=True)
-    finally:
-        if q["reg"]:
-            eng.set_prior(False)
-    ns, form = q["ns"], q["form"]
+    eng, (lev, wt, ps, flags), ns, form = _query("reliability", lambda eng, it: eng.reliability(it, damped=damped, pose_stats=True), iter)
     ms = [int(eng.m[b]) for b in range(len(ns))]
-
-    def shaped(a, counts):
-        if form == "single":
-            return torch.from_numpy(np.ascontiguousarray(a[:1, :counts[0]]))
-        if form == "dense":
-            return torch.from_numpy(np.ascontiguousarray(a[:len(counts), :counts[0]]))
-        return [torch.from_numpy(np.ascontiguousarray(a[b:b + 1, :c])) for b, c in enumerate(counts)]
-
     fl = [int(x) for x in flags[:len(ns)]]
-    reliability.last = dict(flags=fl[0] if form == "single" else fl, pose_stats=shaped(ps, ns))
-    return shaped(lev, ms), shaped(wt, ms)
+    reliability.last = dict(flags=fl[0] if form == "single" else fl, pose_stats=_shaped(ps, ns, form))
+    return _shaped(lev, ms, form), _shaped(wt, ms, form)
 
 
 reliability.last = {}
@@ -772,34 +759,14 @@ def outlier_power(iter=None, damped=False, ncp=17.075, crit=None):
     leverages, the largest finite ``ext_pos``, the rows with ``wtest > crit``.  The device states, damping and the bits of the
     following calls are not changed."""
     import collections
-    import torch
-    q = _cache.get("last_query")
-    eng = _cache.get(q["eng"]) if q is not None else None
-    if eng is None or not getattr(eng, "h", None):
-        raise RuntimeError("outlier_power() needs a preceding BA / BA_reg / BA_window call")
-    it = q["iter"] if iter is None else int(iter)
-    if q["reg"]:
-        eng.set_prior(True)
-    try:
-        *rows, pf, fit, flags = eng.outlier_power(it, damped=damped, ncp=ncp, crit=crit)
-    finally:
-        if q["reg"]:
-            eng.set_prior(False)
-    ns, form = q["ns"], q["form"]
+    eng, (*rows, pf, fit, flags), ns, form = _query("outlier_power", lambda eng, it: eng.outlier_power(it, damped=damped, ncp=ncp, crit=crit),
+                                                    iter)
     ms = [int(eng.m[b]) for b in range(len(ns))]
-
-    def shaped(a, counts):
-        if form == "single":
-            return torch.from_numpy(np.ascontiguousarray(a[:1, :counts[0]]))
-        if form == "dense":
-            return torch.from_numpy(np.ascontiguousarray(a[:len(counts), :counts[0]]))
-        return [torch.from_numpy(np.ascontiguousarray(a[b:b + 1, :c])) for b, c in enumerate(counts)]
-
     Fit = collections.namedtuple("Fit", FIT_FIELDS + ("s0", "flags"))
     recs = [Fit(*[float(x) for x in fit[b]], s0=float(np.sqrt(fit[b, 4])) if fit[b, 4] >= 0 else float("nan"), flags=int(flags[b]))
             for b in range(len(ns))]
-    outlier_power.last = dict(pose_fit=shaped(pf, ns))
-    return (*[shaped(a, ms) for a in rows], recs[0] if form == "single" else recs)
+    outlier_power.last = dict(pose_fit=_shaped(pf, ns, form))
+    return (*[_shaped(a, ms, form) for a in rows], recs[0] if form == "single" else recs)
 
 
 outlier_power.last = {}

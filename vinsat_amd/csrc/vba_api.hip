@@ -402,12 +402,11 @@ int vba_destroy(vba_handle h) {
     if (h->h_back) hipHostFree(h->h_back);
     if (h->h_head) hipHostFree(h->h_head);
     if (h->d_dbg) hipFree(h->d_dbg);
-    if (h->d_cov) hipFree(h->d_cov);
-    if (h->d_rel) hipFree(h->d_rel);
-    if (h->rel_ev) hipEventDestroy(h->rel_ev);
-    if (h->d_pow) hipFree(h->d_pow);
-    if (h->pow_ev) hipEventDestroy(h->pow_ev);
-    for (hipEvent_t e : h->cov_ev) if (e) hipEventDestroy(e);
+    for (QueryScratch* q : {&h->q_cov, &h->q_rel, &h->q_pow}) {
+        if (q->d) hipFree(q->d);
+        if (q->ev) hipEventDestroy(q->ev);
+    }
+    if (h->cov_ev0) hipEventDestroy(h->cov_ev0);
     if (h->arena.base) hipFree(h->arena.base);
     delete h;
     return VBA_OK;

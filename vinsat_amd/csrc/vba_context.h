@@ -4,7 +4,7 @@
 //   vba_schedule.hip     the kernels of one BA() call as the host enqueues them: vba_step, vba_run_schedule (chained calls, graph
 //                        replay), vba_iterate* (pipelined driver loop, host watch)
 //   vba_sharded_api.hip  observation-sharded mode (vba_sh_*)
-//   vba_cov.hip          per-pose marginal covariances (vba_covariance)
+//   vba_cov.hip          per-pose marginal covariances (vba_covariance); the step and the scaffold the three queries share
 //   vba_rel.hip          per-row leverages and w-tests (vba_reliability)
 //   vba_power.hip        per-row detectable biases and influences, the fit's variance factor (vba_outlier_power)
 #pragma once
@@ -29,6 +29,7 @@
 #include "../../include/vinsat_ba.h"
 #include "vba_device.h"
 #include "vba_launch.h"
+#include "vba_query_layout.h"
 
 using namespace vba;
 
@@ -53,6 +54,16 @@ struct Arena {
         used += count * sizeof(T);
         return p;
     }
+};
+
+// What each uncertainty query keeps in the handle: its device scratch (grown on demand, never shrunk), the event behind its last
+// kernel, and the device time of its last call.
+struct QueryScratch {
+    void* d = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    float ms = 0.f;
+    bool ran = false;
 };
 
 struct vba_context {
@@ -151,26 +162,14 @@ struct vba_context {
     int warm_misses = 0;                    // number of calls whose warm select missed and was repeated with the exact digits (diagnostic)
     double* d_dbg = nullptr;                // lazily allocated scratch for debug fetch
     size_t dbg_cap = 0;
-    // vba_covariance (vba_cov.hip): scratch allocated by the first query, its events and the time of the last query
-    void* d_cov = nullptr;
-    size_t cov_cap = 0;
-    hipEvent_t cov_ev[2] = {nullptr, nullptr};
-    float cov_ms = 0.f;
-    bool cov_ran = false;
+    // The uncertainty queries (vba_cov.hip, vba_rel.hip, vba_power.hip): each has a scratch allocated by its first call, and the
+    // time of its last call from cov_ev0, recorded in front of the covariance step all three start with
+    QueryScratch q_cov;                      // the shadow of every array the front of a call writes, Sigma's blocks (cov_layout)
+    QueryScratch q_rel;                      // rel_layout: the two row arrays, the device copy of perm, the pose summary
+    QueryScratch q_pow;                      // pow_layout: four row arrays, the pose and window summaries
+    hipEvent_t cov_ev0 = nullptr;
     bool sharded = false;                   // an observation-sharded call has run (vba_sh_*): no covariance query
-    // vba_reliability (vba_rel.hip): the two row arrays, the device copy of perm and the pose summary, allocated by the first query
-    void* d_rel = nullptr;
-    size_t rel_cap = 0;
-    std::vector<char> perm_stale;           // [W] once a reliability query has run: the device copy of perm[w] predates the last upload
-    hipEvent_t rel_ev = nullptr;
-    float rel_ms = 0.f;
-    bool rel_ran = false;
-    // vba_outlier_power (vba_power.hip): four row arrays, the pose and window summaries, allocated by the first query
-    void* d_pow = nullptr;
-    size_t pow_cap = 0;
-    hipEvent_t pow_ev = nullptr;
-    float pow_ms = 0.f;
-    bool pow_ran = false;
+    std::vector<char> perm_stale;           // [W] once a row pass has run: the device copy of perm[w] predates the last upload
     // Pipelined driver loop (vba_iterate_resident, see iterate_pipelined): the call that was enqueued speculatively behind
     // the one that has just been returned, the chain it belongs to and what has been learnt about the caller's schedule
     struct Spec { bool valid = false; int iter = 0, init = 0; bool reg = false; int c = 0; } spec;
@@ -266,8 +265,8 @@ int vba_set_schedule_graph(vba_handle h, int on);      // (options of vba_set_op
 int vba_set_chain_profile(vba_handle h, int on);
 
 // ---- vba_cov.hip
-// The step the covariance and the reliability query share: the shadow front of a full-phase call and the selected inversion,
-// into the scratch of the query (see vba_cov.hip).
+// The step the three queries share: the shadow front of a full-phase call and the selected inversion, into the scratch of the
+// covariance query (see vba_cov.hip).
 struct CovQuery {
     DevView V;                  // the shadow view: wraw, sc (maximum raw weight of parity V.par) and states are what the row pass reads
     double* diag = nullptr;     // [W][n_max][81] Sigma_ii
@@ -276,12 +275,17 @@ struct CovQuery {
 };
 int cov_begin(vba_handle h, int iter, const char* who);
 int cov_build_invert(vba_handle h, int iter, int damped, CovQuery& q);
+// The scaffold of a query around that step.  query_reserve: q.d holds at least `bytes` (the total of the query's layout,
+// vba_query_layout.h), kept or grown; `what` ends the message of a failed allocation.  query_finish: the end event behind the
+// query's last kernel, the wait for it, q.ms since cov_ev0.  query_last_ms: what the vba_last_*_ms getters return.
+int query_reserve(vba_handle h, QueryScratch& q, size_t bytes, const char* what);
+int query_finish(vba_handle h, QueryScratch& q);
+int query_last_ms(vba_handle h, QueryScratch vba_context::*q, float* ms, const char* none_ran);
 
 // ---- vba_rel.hip
 // What the row passes behind the covariance step share on the host: the device copy of the upload's permutation (sorted position ->
 // input row, [W][m_max], part of the reliability scratch, uploaded for the windows whose rows changed), and the copy of a
 // per-window result to the host (`used[w] * per` doubles of every window's `stride`; the rest stays as the caller left it).
-size_t rel_round(size_t b);
 int rel_device_perm(vba_handle h, const int** d_perm);
-int rel_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per);
+int query_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per);
 #pragma GCC visibility pop

@@ -516,38 +516,78 @@ __global__ __launch_bounds__(64) void k_cov_fix(const int* __restrict__ nw, int 
 
 // ---------------------------------------------------------------------------------------------------------- host side
 
-namespace {
-template <class T>
-T* carve(char*& p, size_t count) {
-    T* q = reinterpret_cast<T*>(p);
-    p += ((count * sizeof(T) + 255) & ~size_t(255));
-    return q;
-}
-}  // namespace
-
-// scratch of the query: the shadow of every array the front of a call writes, and the two [W][n_max][81] result arrays
-static int cov_scratch(vba_handle h) {
-    const size_t W = h->W, N = h->n_max, M = h->m_max;
-    const DevView& V = h->V;
-    const size_t pool = (size_t)V.long_pool_cap;
-    const size_t PR = (size_t)V.p_max;
-    const size_t sizes[] = {W * sizeof(WinScalars), W * 2 * M * 8, W * M * 8, W * 2 * M * 8, W * V.nblk_obs * 8, W * V.trial_stride * 8,
-                            W * V.nblk_obs * 8, W * 2 * V.pred_stride * 8, W * 2 * V.pred_stride * 8, W * 81 * 8, W * kHistStride * 4,
-                            W * N * 21 * 8, W * N * 6 * 8, W * N * (6 + 36 + 6 + 1 + 3 + 9 + 9 + 9) * 8, W * N * 243 * 8, W * N * 9 * 8,
-                            W * N * 10 * 8, W * 2 * pool * 6 * 8, W * N * 81 * 8, W * N * 81 * 8, W * 4,
-                            // partitioned path: X, chunk contributions, separator bands, separator blocks of Sigma
-                            W * N * 162 * 8, W * PR * 243 * 8, W * PR * 243 * 8, W * PR * 81 * 8, W * PR * 81 * 8};
-    size_t need = 0;
-    for (size_t b : sizes) need += (b + 255) & ~size_t(255);
-    if (h->cov_cap >= need) return VBA_OK;
-    if (h->d_cov) (void)hipFree(h->d_cov);
-    h->d_cov = nullptr;
-    h->cov_cap = 0;
-    if (hipMalloc(&h->d_cov, need) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(VBA_ENOMEM, "hipMalloc of " + std::to_string(need) + " bytes of covariance scratch failed");
+// The scratch of the covariance step: the shadow of every array the front of a call writes (into V), and what the selected inversion
+// writes.  Sizes come from V alone, so the counting and the placing run agree by construction.
+struct CovBufs {
+    WinScalars* sc;
+    double* pool;
+    double *diag, *sup;         // the two [W][n_max][81] result arrays
+    unsigned* flags;
+    double *X, *contrib, *sepb, *SSd, *SSs;     // partitioned path: X, chunk contributions, separator bands, separator blocks of Sigma
+};
+static CovBufs cov_layout(Carver& c, DevView& V, size_t W) {
+    const size_t N = V.n_max, M = V.m_max, PR = (size_t)V.p_max;
+    CovBufs b;
+    b.sc = c.take<WinScalars>(W);
+    V.sc = b.sc;
+    V.absr = c.take<double>(W * 2 * M);
+    V.wraw = c.take<double>(W * M);
+    V.ckeys = c.take<double>(W * 2 * M);
+    V.part_init = c.take<double>(W * V.nblk_obs);
+    V.part_trial = c.take<double>(W * V.trial_stride);
+    V.part_next = c.take<double>(W * V.nblk_obs);
+    V.part_pred = c.take<double>(W * 2 * V.pred_stride);
+    V.part_prior = c.take<double>(W * 2 * V.pred_stride);
+    V.lastD = c.take<double>(W * 81);
+    V.hist = c.take<unsigned>(W * kHistStride);
+    V.Hraw = c.take<double>(W * N * 21);
+    V.braw = c.take<double>(W * N * 6);
+    {
+        double* d = c.take<double>(W * N * (6 + 36 + 6 + 1 + 3 + 9 + 9 + 9));
+        V.xhat = d; d += W * N * 6; V.Phi = d; d += W * N * 36; V.rorb = d; d += W * N * 6; V.fatt = d; d += W * N;
+        V.qgrad = d; d += W * N * 3; V.Hd = d; d += W * N * 9; V.Hu = d; d += W * N * 9; V.Hl = d;
     }
-    h->cov_cap = need;
+    V.bands = c.take<double>(W * N * 243);
+    V.rhs = c.take<double>(W * N * 9);
+    V.states_new = c.take<double>(W * N * 10);
+    b.pool = c.take<double>(W * 2 * (size_t)V.long_pool_cap * 6);
+    b.diag = c.take<double>(W * N * 81);
+    b.sup = c.take<double>(W * N * 81);
+    b.flags = c.take<unsigned>(W);
+    b.X = c.take<double>(W * N * 162);
+    b.contrib = c.take<double>(W * PR * 243);
+    b.sepb = c.take<double>(W * PR * 243);
+    b.SSd = c.take<double>(W * PR * 81);
+    b.SSs = c.take<double>(W * PR * 81);
+    return b;
+}
+
+int query_reserve(vba_handle h, QueryScratch& q, size_t bytes, const char* what) {
+    if (q.cap >= bytes) return VBA_OK;
+    if (q.d) (void)hipFree(q.d);
+    q.d = nullptr;
+    q.cap = 0;
+    if (hipMalloc(&q.d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VBA_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes of " + what);
+    }
+    q.cap = bytes;
+    return VBA_OK;
+}
+
+int query_finish(vba_handle h, QueryScratch& q) {
+    if (!q.ev) HIPCHK(hipEventCreate(&q.ev));
+    HIPCHK(hipEventRecord(q.ev, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipEventElapsedTime(&q.ms, h->cov_ev0, q.ev));
+    q.ran = true;
+    return VBA_OK;
+}
+
+int query_last_ms(vba_handle h, QueryScratch vba_context::*q, float* ms, const char* none_ran) {
+    if (!h || !ms) return fail(VBA_EINVAL, "null argument");
+    if (!(h->*q).ran) return fail(VBA_ESTATE, none_ran);
+    *ms = (h->*q).ms;
     return VBA_OK;
 }
 
@@ -564,56 +604,25 @@ int cov_begin(vba_handle h, int iter, const char* who) {
 }
 
 // The shadow front and the selected inversion, enqueued on the handle's stream into the scratch of the query: the step
-// vba_covariance and vba_reliability (vba_rel.hip) share.  cov_ev[0] is recorded in front of it; the caller records its own end
-// event and synchronises.  q: the shadow view (its wraw, its window scalars with the maximum raw weight and its bands stay valid
+// vba_covariance, vba_reliability (vba_rel.hip) and vba_outlier_power (vba_power.hip) share.  cov_ev0 is recorded in front of it;
+// the caller ends with query_finish.  q: the shadow view (its wraw, its window scalars with the maximum raw weight and its bands stay valid
 // until the next query) and the device results.
 int cov_build_invert(vba_handle h, int iter, int damped, CovQuery& q) {
-    if (int rc = cov_scratch(h)) return rc;
     hipStream_t s = h->stream;
-    if (!h->cov_ev[0]) {
-        HIPCHK(hipEventCreate(&h->cov_ev[0]));
-        HIPCHK(hipEventCreate(&h->cov_ev[1]));
-    }
-    const size_t W = h->W, N = h->n_max, M = h->m_max;
+    const size_t W = h->W;
     // the shadow view: the view of the next call (parity h->par, full phase, nothing carried, nothing emitted) with every array
     // the front writes redirected into the scratch
     CallSpec c;
     c.iter = iter; c.initialize = 0; c.call = -1; c.par = h->par; c.emit = 0; c.carry = 0;
     DevView& V = q.V;
     view_for_call(h, V, c);
-    char* p = reinterpret_cast<char*>(h->d_cov);
-    WinScalars* sc = carve<WinScalars>(p, W);
-    V.sc = sc;
-    V.absr = carve<double>(p, W * 2 * M);
-    V.wraw = carve<double>(p, W * M);
-    V.ckeys = carve<double>(p, W * 2 * M);
-    V.part_init = carve<double>(p, W * V.nblk_obs);
-    V.part_trial = carve<double>(p, W * V.trial_stride);
-    V.part_next = carve<double>(p, W * V.nblk_obs);
-    V.part_pred = carve<double>(p, W * 2 * V.pred_stride);
-    V.part_prior = carve<double>(p, W * 2 * V.pred_stride);
-    V.lastD = carve<double>(p, W * 81);
-    V.hist = carve<unsigned>(p, W * kHistStride);
-    V.Hraw = carve<double>(p, W * N * 21);
-    V.braw = carve<double>(p, W * N * 6);
-    {
-        double* d = carve<double>(p, W * N * (6 + 36 + 6 + 1 + 3 + 9 + 9 + 9));
-        V.xhat = d; d += W * N * 6; V.Phi = d; d += W * N * 36; V.rorb = d; d += W * N * 6; V.fatt = d; d += W * N;
-        V.qgrad = d; d += W * N * 3; V.Hd = d; d += W * N * 9; V.Hu = d; d += W * N * 9; V.Hl = d;
-    }
-    V.bands = carve<double>(p, W * N * 243);
-    V.rhs = carve<double>(p, W * N * 9);
-    V.states_new = carve<double>(p, W * N * 10);
-    double* pool = carve<double>(p, W * 2 * (size_t)V.long_pool_cap * 6);
-    double* d_diag = carve<double>(p, W * N * 81);
-    double* d_sup = carve<double>(p, W * N * 81);
-    unsigned* d_flags = carve<unsigned>(p, W);
-    const size_t PR = (size_t)h->V.p_max;
-    double* d_X = carve<double>(p, W * N * 162);
-    double* d_contrib = carve<double>(p, W * PR * 243);
-    double* d_sepb = carve<double>(p, W * PR * 243);
-    double* d_SSd = carve<double>(p, W * PR * 81);
-    double* d_SSs = carve<double>(p, W * PR * 81);
+    Carver count;
+    cov_layout(count, V, W);
+    if (int rc = query_reserve(h, h->q_cov, count.total(), "covariance scratch failed")) return rc;
+    if (!h->cov_ev0) HIPCHK(hipEventCreate(&h->cov_ev0));
+    Carver place{static_cast<char*>(h->q_cov.d)};
+    const CovBufs b = cov_layout(place, V, W);
+    const size_t PR = (size_t)V.p_max;
     V.wbucket = nullptr;            // nothing carried: the bin buckets are neither read nor written
     V.wmax_ext = nullptr;
     V.hist0_ext[0] = V.hist0_ext[1] = nullptr;
@@ -626,11 +635,11 @@ int cov_build_invert(vba_handle h, int iter, int damped, CovQuery& q) {
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipMemcpy(hsc.data(), h->V.sc, W * sizeof(WinScalars), hipMemcpyDeviceToHost));
     for (auto& x : hsc) { x.miss = 0; x.call_idx = 0; x.pending = -1; }
-    HIPCHK(hipMemcpyAsync(sc, hsc.data(), W * sizeof(WinScalars), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(h->cov_ev[0], s));
+    HIPCHK(hipMemcpyAsync(b.sc, hsc.data(), W * sizeof(WinScalars), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(h->cov_ev0, s));
     if (V.nblk_long > 0)
-        HIPCHK(hipMemcpyAsync(pool, h->V.long_pool, W * 2 * (size_t)V.long_pool_cap * 6 * 8, hipMemcpyDeviceToDevice, s));
-    V.long_pool = pool;
+        HIPCHK(hipMemcpyAsync(b.pool, h->V.long_pool, W * 2 * (size_t)V.long_pool_cap * 6 * 8, hipMemcpyDeviceToDevice, s));
+    V.long_pool = b.pool;
     HIPCHK(hipMemsetAsync(V.hist, 0, W * kHistStride * 4, s));
     // the front of a full-phase call with nothing carried (enqueue_front, the profiled order), then the assembly
     launch_obs_residual(V, nullptr, s);
@@ -645,21 +654,21 @@ int cov_build_invert(vba_handle h, int iter, int damped, CovQuery& q) {
     const int s_chunk = h->V.chunk;
     if (s_chunk >= 2) {
         const int pc = (h->n_max + s_chunk - 1) / s_chunk;
-        HIPCHK(hipMemsetAsync(d_flags, 0, W * 4, s));
+        HIPCHK(hipMemsetAsync(b.flags, 0, W * 4, s));
         hipLaunchKernelGGL(k_cov_chunk, dim3(pc, h->W), dim3(64), 0, s, V.bands, V.n, h->n_max, s_chunk, h->V.sc, h->par, damped ? 1 : 0,
-                           d_diag, d_sup, d_X, d_contrib, (int)PR, d_flags);
+                           b.diag, b.sup, b.X, b.contrib, (int)PR, b.flags);
         hipLaunchKernelGGL(k_cov_sep, dim3(h->W), dim3(64), 0, s, V.bands, V.n, h->n_max, s_chunk, h->V.sc, h->par, damped ? 1 : 0,
-                           d_contrib, d_sepb, (int)PR, d_SSd, d_SSs, d_flags);
-        hipLaunchKernelGGL(k_cov_fix, dim3(pc, h->W), dim3(64), 0, s, V.n, h->n_max, s_chunk, d_diag, d_sup, d_X, d_SSd, d_SSs, (int)PR,
-                           d_flags);
+                           b.contrib, b.sepb, (int)PR, b.SSd, b.SSs, b.flags);
+        hipLaunchKernelGGL(k_cov_fix, dim3(pc, h->W), dim3(64), 0, s, V.n, h->n_max, s_chunk, b.diag, b.sup, b.X, b.SSd, b.SSs, (int)PR,
+                           b.flags);
     } else {
-        hipLaunchKernelGGL(k_cov_seq, dim3(h->W), dim3(64), 0, s, V.bands, V.n, h->n_max, h->V.sc, h->par, damped ? 1 : 0, d_diag, d_sup,
-                           d_flags);
+        hipLaunchKernelGGL(k_cov_seq, dim3(h->W), dim3(64), 0, s, V.bands, V.n, h->n_max, h->V.sc, h->par, damped ? 1 : 0, b.diag, b.sup,
+                           b.flags);
     }
     HIPCHK(hipGetLastError());
-    q.diag = d_diag;
-    q.sup = d_sup;
-    q.flags = d_flags;
+    q.diag = b.diag;
+    q.sup = b.sup;
+    q.flags = b.flags;
     return VBA_OK;
 }
 
@@ -667,21 +676,12 @@ int vba_covariance(vba_handle h, int iter, int damped, double* diag, double* sup
     if (int rc = cov_begin(h, iter, "vba_covariance")) return rc;
     CovQuery q;
     if (int rc = cov_build_invert(h, iter, damped, q)) return rc;
-    hipStream_t s = h->stream;
+    if (int rc = query_finish(h, h->q_cov)) return rc;
     const size_t W = h->W, N = h->n_max;
-    HIPCHK(hipEventRecord(h->cov_ev[1], s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&h->cov_ms, h->cov_ev[0], h->cov_ev[1]));
-    h->cov_ran = true;
     if (diag) HIPCHK(hipMemcpy(diag, q.diag, W * N * 81 * 8, hipMemcpyDeviceToHost));
     if (super) HIPCHK(hipMemcpy(super, q.sup, W * N * 81 * 8, hipMemcpyDeviceToHost));
     if (flags) HIPCHK(hipMemcpy(flags, q.flags, W * 4, hipMemcpyDeviceToHost));
     return VBA_OK;
 }
 
-int vba_last_covariance_ms(vba_handle h, float* ms) {
-    if (!h || !ms) return fail(VBA_EINVAL, "null argument");
-    if (!h->cov_ran) return fail(VBA_ESTATE, "no covariance query has run");
-    *ms = h->cov_ms;
-    return VBA_OK;
-}
+int vba_last_covariance_ms(vba_handle h, float* ms) { return query_last_ms(h, &vba_context::q_cov, ms, "no covariance query has run"); }

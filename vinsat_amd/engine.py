@@ -272,10 +272,14 @@ class BAEngine:
         _lib.check(self.lib.vba_chain_profile(self.h, ms, cnt, int(bool(reset))), self.lib)
         return {k: ((ms[i] / cnt[i]) if cnt[i] else 0.0, int(cnt[i])) for i, k in enumerate(self.CHAIN_CLASSES)}
 
-    def last_step_ms(self):
+    def _last_ms(self, name):
+        """Device time of the last ``name`` (``vba_last_<name>_ms``)."""
         ms = c_float()
-        _lib.check(self.lib.vba_last_step_ms(self.h, byref(ms)), self.lib)
+        _lib.check(getattr(self.lib, f"vba_last_{name}_ms")(self.h, byref(ms)), self.lib)
         return ms.value
+
+    def last_step_ms(self):
+        return self._last_ms("step")
 
     FLAG_ZERO_PIVOT, FLAG_NONFINITE, FLAG_INDEFINITE = 4, 2, 8
 
@@ -294,9 +298,7 @@ class BAEngine:
         return (diag, sup, flags) if super_diagonal else (diag, flags)
 
     def last_covariance_ms(self):
-        ms = c_float()
-        _lib.check(self.lib.vba_last_covariance_ms(self.h, byref(ms)), self.lib)
-        return ms.value
+        return self._last_ms("covariance")
 
     def reliability(self, it, damped=False, pose_stats=False):
         """``vba_reliability``: per observation row of every window, at the resident states, the leverage ``tr(P_k)`` and the
@@ -316,9 +318,7 @@ class BAEngine:
         return (lev, wt, ps, flags) if pose_stats else (lev, wt, flags)
 
     def last_reliability_ms(self):
-        ms = c_float()
-        _lib.check(self.lib.vba_last_reliability_ms(self.h, byref(ms)), self.lib)
-        return ms.value
+        return self._last_ms("reliability")
 
     def outlier_power(self, it, damped=False, ncp=17.075, crit=None):
         """``vba_outlier_power``: per observation row of every window, at the resident states, the minimal detectable bias
@@ -342,9 +342,7 @@ class BAEngine:
         return (*rows, pf, fit, flags)
 
     def last_outlier_power_ms(self):
-        ms = c_float()
-        _lib.check(self.lib.vba_last_outlier_power_ms(self.h, byref(ms)), self.lib)
-        return ms.value
+        return self._last_ms("outlier_power")
 
     def debug(self, what, window=0):
         n, m = self.n[window], self.m[window]
