@@ -537,7 +537,8 @@ int vba_schur_get_state(vba_schur_handle h, double* states, double* landmarks);
  * A reduced camera system that is not positive definite at this damping is a REJECTED trial (*accepted = 0, *cost_after =
  * *cost_before, state untouched; vba_schur_last_info tells the failing row): the caller raises lamda as after any rejection. */
 int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, double* cost_after, int* accepted);
-/* 0 if the last factorisation went through, else 1 + the row of the reduced system at which it met a non-positive pivot */
+/* 0 if the last factorisation went through, else 1 + the row of the reduced system at which it met a non-positive pivot
+ * (the first such row: the factorisation goes on with that pivot replaced by 1, what it meets later is not recorded) */
 int vba_schur_last_info(vba_schur_handle h, int* info);
 /* HIP-event times of the last iterate: build (blocks + Schur complement), factor (Cholesky), solve (substitutions + update) */
 int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, float* solve_ms);

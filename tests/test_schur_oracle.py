@@ -4,6 +4,7 @@ back to the truth from a perturbed start -- and the host-side index structure th
 import numpy as np
 import pytest
 
+import schur_cases as C
 from oracle import schur_oracle as S
 from vinsat_amd import synth
 from vinsat_amd.schur import build_structure
@@ -54,8 +55,14 @@ def test_lm_on_the_oracle_recovers_poses_and_landmarks(prob):
 
 
 def test_index_structure_covers_every_pair_once(prob):
-    d = prob
-    n, L = d["states_gt"].shape[0], d["X_true"].shape[0]
+    for name in ("base", "wide", "pose_without_rows", "more_landmarks_than_rows"):
+        _check_index_structure(prob if name == "base" else C.case(name), name)
+    with pytest.raises(ValueError):
+        build_structure(np.array([0, 0]), np.array([1, 1]), 2, 2)      # one landmark twice from one pose
+
+
+def _check_index_structure(d, name):
+    n, L = d["states_gt"].shape[0], d["X0"].shape[0]
     order, s = build_structure(d["pose_of_row"], d["landmark_of_row"], n, L)
     rp, rl = d["pose_of_row"][order], d["landmark_of_row"][order]
     assert np.array_equal(s["row_pose"], rp) and np.array_equal(s["row_lm"], rl)
@@ -72,5 +79,75 @@ def test_index_structure_covers_every_pair_once(prob):
     # every unordered pair of rows of a landmark (and every row with itself) appears exactly once
     cnt = np.diff(s["lm_ptr"]).astype(np.int64)
     assert s["pair_k"].size == int((cnt * (cnt + 1) // 2).sum())
-    with pytest.raises(ValueError):
-        build_structure(np.array([0, 0]), np.array([1, 1]), 2, 2)      # one landmark twice from one pose
+    # ... by brute force: the pair list of every block is exactly the set of row pairs that share a landmark
+    want = C.pairs_by_brute_force(rp, rl, L)
+    for b in range(s["blk_i"].size):
+        lo, hi = s["blk_ptr"][b], s["blk_ptr"][b + 1]
+        got = list(zip(s["pair_k"][lo:hi].tolist(), s["pair_k2"][lo:hi].tolist()))
+        assert len(got) == len(set(got)) and set(got) == want.pop((int(s["blk_i"][b]), int(s["blk_j"][b])), set())
+    assert not want
+    # CSR of the rows of a landmark / of a pose: exactly the rows that name it (empty for a pose without rows, for an unobserved landmark)
+    assert np.array_equal(np.diff(s["lm_ptr"]), np.bincount(rl, minlength=L)) and np.array_equal(np.diff(s["pose_ptr"]), np.bincount(rp, minlength=n))
+    if name == "pose_without_rows":
+        i = d["empty_pose"]
+        assert s["pose_ptr"][i] == s["pose_ptr"][i + 1] and not np.any((s["blk_i"] == i) ^ (s["blk_j"] == i))
+    if name == "more_landmarks_than_rows":
+        assert L > rp.size and np.all(np.diff(s["lm_ptr"])[d["unobserved"]] == 0)
+    if name == "wide":
+        assert C.tile_bandwidth(s) == (6 * n + 63) // 64 - 1
+
+
+FLOOR_CASES = [(n, lam) for n in C.NARROW for lam in (1e-3, 1e-6)] + [("wide", 1e-3)] + [(n, 1e-3) for n in C.EDGES[:3]] + [(C.EDGES[3], 1e4)]
+
+
+@pytest.mark.parametrize("name,lam", FLOOR_CASES)
+def test_the_two_routes_agree_on_every_problem_of_the_gpu_tests(name, lam):
+    """The noise floor of the reference the GPU tests compare with (bars 1e-7 on dc and dl): its two routes agree to a tenth of
+    the bar on every problem, at the damping used there.  On the narrow-band problems the factor keeps the band exactly."""
+    r = C.reference(name, lam, True)
+    print(f"FLOOR {name} lam={lam:g} dc={r.floor_dc:.2e} dl={r.floor_dl:.2e}")
+    assert r.floor_dc < 1e-8 and r.floor_dl < 1e-8
+    assert np.linalg.eigvalsh(r.Sm).min() > 0
+    if name in C.NARROW:
+        bw = C.tile_bandwidth(C.structure(C.case(name)))
+        skipped, zero = C.tiles_beyond_band_are_zero(r.Lc, bw)
+        assert bw == 2 and skipped > 0 and zero
+
+
+def test_clamped_rows_are_clamped_and_a_minor_part_of_the_cost():
+    from oracle import ba_oracle as O
+    d = C.case("behind_the_camera")
+    k = d["clamped_rows"]
+    ii, X = d["pose_of_row"][k], d["Xs"][d["landmark_of_row"][k]]
+    # behind the camera: the projection is the clamped one and does not depend on the depth
+    est = O.landmark_project(d["states0"], X, d["intrinsics"], ii, jacobian=False)
+    q = d["states0"][ii, 3:7]
+    axis = O.rotation_matrix(q / np.linalg.norm(q, axis=1, keepdims=True))[:, :, 2]
+    assert np.all(np.einsum("kj,kj->k", X - d["states0"][ii, :3], axis) < -0.9)
+    assert np.abs(O.landmark_project(d["states0"], X - 0.5 * axis, d["intrinsics"], ii, jacobian=False) - est).max() < 1e-6
+    keep = np.ones(d["uv"].shape[0], dtype=bool)
+    keep[k] = False
+    others = S.cost(d["states0"], d["Xs"], d["X0"], d["uv"][keep], d["w"][keep], d["pose_of_row"][keep], d["landmark_of_row"][keep],
+                    d["intrinsics"], d["sigma"])
+    c0 = C.reference("behind_the_camera", 1e4, True).c0
+    assert 0 < c0 - others < 0.5 * c0
+
+
+def test_late_failure_is_unambiguous():
+    """The case behind tests/test_schur_gpu.py::test_last_info_tells_the_first_failing_row: the first bad pivot is in the
+    third panel, at the first row of the first pose with negative weights, and no rounding decides it.
+
+    The margin first proposed for this -- every pivot further than 1e-6 max|diag S| from zero -- cannot hold for this geometry
+    at lam = 0, with any seed: the rotation diagonals are 1.4e10 .. 3.5e10 (a 500 km lever arm, squared) and the position
+    pivots 1e2 .. 1e3, which is 3e-3 .. 1e-2 of that margin; the failing pivot is -0.04 .. -0.1 of it (seeds 1 .. 5).  What is
+    asserted instead: a symmetric perturbation of S by 1e-9 of every entry -- a hundred times the 1e-11 to which the device's
+    Lg Lg^T agrees with the oracle's S wherever the two can be compared -- moves no pivot up to the failing one by 1 % and
+    leaves the failing row where it is; and the failing pivot is larger in size than the smallest pivot before it."""
+    Sm, row, piv = C.late_failure_reference()
+    assert 512 <= row < 768 and row == 6 * (129 - 30)
+    assert piv[-1] < 0 and abs(piv[-1]) > piv[:-1].min() > 0
+    rng = np.random.default_rng(0)
+    for _ in range(3):
+        P = np.tril(rng.uniform(-1e-9, 1e-9, Sm.shape))
+        row2, piv2 = C.first_bad_pivot(Sm * (1.0 + P + np.tril(P, -1).T))
+        assert row2 == row and np.all(np.abs(piv2 / piv - 1.0) < 1e-2)

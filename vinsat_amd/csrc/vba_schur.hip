@@ -277,17 +277,19 @@ __global__ __launch_bounds__(64) void k_potrf64(SchurView V, int kb, int* info) 
     double a[kT];
 #pragma unroll
     for (int c = 0; c < kT; ++c) a[c] = At[(size_t)r * V.Npad + c];     // (the upper part is never used)
-    bool bad = false;
+    int bad = -1;                   // first column with a non-positive pivot (the same in every lane)
 #pragma unroll
     for (int j = 0; j < kT; ++j) {
         const double d = bcast64(a[j], j);
-        if (!(d > 0.0)) bad = true;
+        if (!(d > 0.0) && bad < 0) bad = j;
         const double sd = sqrt(d > 0.0 ? d : 1.0), isd = 1.0 / sd;
         a[j] = r == j ? sd : a[j] * isd;            // column j: L[r][j] for r > j (rows above j hold garbage there, never read)
 #pragma unroll
         for (int c = j + 1; c < kT; ++c) a[c] = fma(-a[j], bcast64(a[j], c), a[c]);     // A[r][c] -= L[r][j] L[c][j]; used for r >= c
     }
-    if (bad && r == 0) *info = kb * kT + 1;
+    // the FIRST failing row of the whole factorisation stays on record: the tile launches are ordered on one stream, and only
+    // that pivot means anything (later ones follow a pivot replaced by 1)
+    if (bad >= 0 && r == 0 && *info == 0) *info = kb * kT + bad + 1;
 #pragma unroll
     for (int c = 0; c < kT; ++c)
         if (c <= r) At[(size_t)r * V.Npad + c] = a[c];
@@ -339,6 +341,7 @@ __global__ __launch_bounds__(256) void k_potrf64b(SchurView V, int kb, int* info
         X[r * LD + c] = 0.0;
     }
     __syncthreads();
+    int bad_row = -1;               // wave 0: first row of this tile with a non-positive pivot
     for (int jb = 0; jb < 4; ++jb) {
         const int o = 16 * jb;
         if (wv == 0) {      // diagonal block: factor and inverse, row per lane (lanes 16 .. 63 ride along on an identity)
@@ -346,17 +349,15 @@ __global__ __launch_bounds__(256) void k_potrf64b(SchurView V, int kb, int* info
             double a[16], x[16];
 #pragma unroll
             for (int c = 0; c < 16; ++c) a[c] = r < 16 ? T[(o + r) * LD + o + c] : (c == (r & 15) ? 1.0 : 0.0);
-            bool bad = false;
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const double d = bcast64(a[j], j);
-                if (!(d > 0.0)) bad = true;
+                if (!(d > 0.0) && bad_row < 0) bad_row = o + j;
                 const double sd = sqrt(d > 0.0 ? d : 1.0), isd = 1.0 / sd;
                 a[j] = r == j ? sd : a[j] * isd;
 #pragma unroll
                 for (int c = j + 1; c < 16; ++c) a[c] = fma(-a[j], bcast64(a[j], c), a[c]);
             }
-            if (bad && r == 0) *info = kb * kT + o + 1;
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) {
                 double sacc = rr == r ? 1.0 : 0.0;
@@ -419,6 +420,7 @@ __global__ __launch_bounds__(256) void k_potrf64b(SchurView V, int kb, int* info
         }
         __syncthreads();
     }
+    if (t == 0 && bad_row >= 0 && *info == 0) *info = kb * kT + bad_row + 1;       // (the first failing row stays, as in k_potrf64)
     double* out = V.invL + (size_t)kb * kT * kT;
     for (int e = t; e < kT * kT; e += 256) {
         const int r = e >> 6, c = e & 63;

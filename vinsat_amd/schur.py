@@ -131,7 +131,7 @@ class SchurBA:
         return c0.value, c1.value, bool(acc.value)
 
     def last_info(self):
-        """0 if the last factorisation went through, else 1 + the row at which it met a non-positive pivot."""
+        """0 if the last factorisation went through, else 1 + the row at which it first met a non-positive pivot."""
         v = c_int()
         self._check(self.lib.vba_schur_last_info(self.h, byref(v)))
         return v.value
