@@ -2,6 +2,9 @@
 #include "vba_context.h"
 
 thread_local std::string g_err;
+#ifdef VBA_ENTRY_STAMPS
+EntryStamps g_estamps;
+#endif
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
@@ -36,6 +39,7 @@ int check_window(vba_handle h, int window) {
 // k_decide wrote the outcome of the trial into mapped host memory; waiting for the stream is all that is needed
 int read_heads(vba_handle h) {
     HIPCHK(hipStreamSynchronize(h->stream));
+    VBA_ESTAMP(0);
     for (int w = 0; w < h->W; ++w)
         if (h->h_head[w].flags & 64u)       // k_solve_resident: a consumer block gave up waiting for its producers
             return fail(VBA_ESTATE, "resident solve: a block of window " + std::to_string(w) + " timed out waiting for its producers (vba_set_fusion bits 5, 6)");
@@ -67,8 +71,24 @@ hipError_t create_aux_stream(hipStream_t* s) {
 // front and its first trial but nobody decided it: its input states, the result the caller holds, are intact (call
 // parity), its trial states and everything keyed to them are dropped.  `boundary`: the caller left the resident loop
 // (uploads, new states): remember not to speculate behind a call with that iter again.
-int settle(vba_handle h, bool boundary) {
+// The states that vba_set_states staged for the first kernel of a chained schedule, sent up with the two stream copies of the other
+// handles instead: whoever else is about to read S[par] or the damping -- a single call, a query, the sharded calls, vba_get_states
+// -- comes through settle() and finds them on the device.
+int flush_states(vba_handle h) {
+    if (!h->pend.on) return VBA_OK;
+    h->pend.on = false;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n10 = (size_t)h->pend.n * 10;
+    HIPCHK(hipMemcpyAsync(h->S[h->pend.par], h->h_stage_map, n10 * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(&h->V.sc[0].lam[h->pend.par], h->h_stage_map + n10, 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->ev_stage, h->stream));
+    h->stage_copy = true;
+    return VBA_OK;
+}
+
+int settle(vba_handle h, bool boundary, bool keep_staged) {
     if (!h) return VBA_OK;
+    if (!keep_staged) { if (int rc = flush_states(h)) return rc; }
     if (!h->spec.valid) {
         // the caller left the resident loop behind a call that had speculated nothing: what it does next is not "what follows
         // that iter" (learning across a window boundary made every second window waste a speculated call)
@@ -326,6 +346,8 @@ int vba_create_mode(int device, int windows, int n_max, int64_t m_max, int mode,
     if ((windows == 1 && (hipEventCreateWithFlags(&h->ev_first, hipEventDisableTiming) != hipSuccess ||
                           hipHostMalloc((void**)&h->h_states_map, (size_t)2 * n_max * 10 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
                           hipHostGetDevicePointer((void**)&h->V.host_states, h->h_states_map, 0) != hipSuccess)) ||
+        (windows == 1 && lat && (hipHostMalloc((void**)&h->h_stage_map, ((size_t)n_max * 10 + 2) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+                                 hipHostGetDevicePointer((void**)&h->d_stage_map, h->h_stage_map, 0) != hipSuccess)) ||
         hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
         (!lat && create_aux_stream(&h->aux_stream) != hipSuccess) ||
         hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
@@ -379,6 +401,7 @@ int vba_get_mode(vba_handle h, int* mode, int* chunk) {
 
 int vba_destroy(vba_handle h) {
     if (!h) return VBA_OK;
+    h->pend.on = false;
     (void)settle(h);
     watch_stop(h);
     hipSetDevice(h->device);
@@ -389,6 +412,7 @@ int vba_destroy(vba_handle h) {
     for (auto& ge : h->graphs) if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
     if (h->ev_first) hipEventDestroy(h->ev_first);
     if (h->h_states_map) hipHostFree(h->h_states_map);
+    if (h->h_stage_map) hipHostFree(h->h_stage_map);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
     if (h->ev0) hipEventDestroy(h->ev0);
@@ -415,6 +439,7 @@ int vba_destroy(vba_handle h) {
 int vba_set_solver2(vba_handle h, int chunk, int chunk2) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (chunk < 2 || chunk > 60 || (chunk2 != 0 && chunk2 != -1 && (chunk2 < 2 || chunk2 > 60)))
         return fail(VBA_EINVAL, "chunk sizes must be in [2, 60] (chunk2 = 0: single level, -1: cyclic reduction)");
     if (chunk2 == -1 && (h->n_max + chunk - 1) / chunk - 1 > 128)
@@ -428,6 +453,7 @@ int vba_set_solver2(vba_handle h, int chunk, int chunk2) {
 int vba_set_solver(vba_handle h, int chunk) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     h->V.chunk2 = 0;
     if (chunk == -1) {      // default: many windows supply their own parallelism (one wave walks each chain);
         h->no_pack = 0;     // otherwise the chain is cut into chunks and the reduced system over the (at most 64)
@@ -487,6 +513,7 @@ int vba_set_solver(vba_handle h, int chunk) {
 int vba_set_integrator(vba_handle h, int hop100) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     h->V.hop = hop100 ? 1 : 0;
     h->V.nblk_long = h->V.hop ? 0 : *std::max_element(h->n_long.begin(), h->n_long.end());
     return VBA_OK;
@@ -495,6 +522,7 @@ int vba_set_integrator(vba_handle h, int hop100) {
 static int vba_set_accumulate_lanes(vba_handle h, int lanes) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (lanes == 0) {
         const double avg = (double)h->m_max / (double)h->n_max;
         int G = 4;
@@ -517,6 +545,7 @@ static int vba_set_accumulate_lanes(vba_handle h, int lanes) {
 static int vba_set_trial_tiles(vba_handle h, int tiles) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (tiles == 0) {
         const int64_t blocks = (int64_t)h->W * h->V.nblk_obs;
         tiles = blocks >= 600 ? 4 : (blocks >= 150 ? 2 : 1);
@@ -529,6 +558,7 @@ static int vba_set_trial_tiles(vba_handle h, int tiles) {
 static int vba_set_key_carry(vba_handle h, int on) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     h->carry_enabled = on != 0;
     h->carry_ok = false;
     return VBA_OK;
@@ -537,6 +567,7 @@ static int vba_set_key_carry(vba_handle h, int on) {
 static int vba_set_fusion(vba_handle h, int mask) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (mask < 0 || mask > 127) return fail(VBA_EINVAL, "mask must be in [0, 127]");
 #ifndef VBA_VARIANTS
     if (mask & (16 | 32 | 64)) return fail(VBA_EINVAL, "mask bits 4 .. 6 select comparison variants that this build does not carry (make VARIANTS=1)");
@@ -549,6 +580,7 @@ static int vba_set_fusion(vba_handle h, int mask) {
 static int vba_set_chunk_waves(vba_handle h, int waves) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (waves != 1 && waves != 2) return fail(VBA_EINVAL, "waves must be 1 or 2");
     h->chunk_waves = waves;
     return VBA_OK;
@@ -557,6 +589,7 @@ static int vba_set_chunk_waves(vba_handle h, int waves) {
 static int vba_set_warm_select(vba_handle h, int on) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     h->warm_enabled = on == 2 ? 2 : (on != 0);
     h->inline_select = on != 3;     // 3: warm select as its own kernel (k_select_warm), the round-2 mid-point; comparison / tests
     return VBA_OK;
@@ -565,6 +598,7 @@ static int vba_set_warm_select(vba_handle h, int on) {
 static int vba_set_warm_shift(vba_handle h, int shift) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (shift < 42 || shift > 51) return fail(VBA_EINVAL, "shift must be in [42, 51]");
     h->V.warm_shift = shift;
     h->carry_ok = 0;            // a histogram binned with another width cannot be resolved
@@ -574,6 +608,7 @@ static int vba_set_warm_shift(vba_handle h, int shift) {
 static int vba_set_bucket_cap(vba_handle h, int cap) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (!h->bucket_cap_alloc) return fail(VBA_ESTATE, "this handle has no bin buckets (16 windows or more)");
     if (cap != 0 && (cap < 8 || cap > h->bucket_cap_alloc)) return fail(VBA_EINVAL, "cap must be 0 (default) or in [8, allocated capacity]");
     h->V.bucket_cap = cap ? cap : h->bucket_cap_alloc;
@@ -594,6 +629,7 @@ int vba_set_host_watch(vba_handle h, int slot, const void* live, const void* cop
 static int vba_set_pipeline(vba_handle h, int on) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc = settle(h)) return rc;
+    h->touch();
     h->pipeline = on != 0;
     return VBA_OK;
 }
@@ -616,6 +652,7 @@ int vba_warm_select_misses(vba_handle h, int* count) {
 static int vba_set_jacobian_f32(vba_handle h, int on) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (on != 0 && on != 1) return fail(VBA_EINVAL, "jacobian_f32 must be 0 (fp64, default) or 1 (fp32)");
     h->V.jac_f32 = on;
     return VBA_OK;
@@ -624,6 +661,7 @@ static int vba_set_jacobian_f32(vba_handle h, int on) {
 static int vba_set_pivoting(vba_handle h, int always) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     h->pivot_mode = always ? 1 : 0;
     return VBA_OK;
 }
@@ -637,6 +675,7 @@ int vba_solver_fallbacks(vba_handle h, int* count) {
 int vba_set_stream(vba_handle h, void* hip_stream, int external) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     hipStreamSynchronize(h->stream);
     h->stream = external ? (hipStream_t)hip_stream : h->own_stream;
     return VBA_OK;
@@ -646,6 +685,7 @@ int vba_upload_observations(vba_handle h, int window, int n, int64_t m, const do
                             const double* conf, const int64_t* ii) {
     if (int rc = check_window(h, window)) return rc;
     if (int rc_settle = settle(h, true)) return rc_settle;
+    h->touch();
     if (!xyz || !uv || !conf || !ii) return fail(VBA_EINVAL, "null observation array");
     h->carry_ok = false;
     if (n < 2 || n > h->n_max) return fail(VBA_EINVAL, "n out of range (need 2 <= n <= n_max)");
@@ -701,6 +741,7 @@ int vba_upload_window(vba_handle h, int window, int n, const double* intrinsics,
                       const int64_t* time_idx) {
     if (int rc = check_window(h, window)) return rc;
     if (int rc_settle = settle(h, true)) return rc_settle;
+    h->touch();
     if (!intrinsics || !cumrot_last || !time_idx) return fail(VBA_EINVAL, "null pose-constant array");
     h->carry_ok = false;
     if (n < 2 || n > h->n_max) return fail(VBA_EINVAL, "n out of range (need 2 <= n <= n_max)");
@@ -768,6 +809,7 @@ int vba_upload_window(vba_handle h, int window, int n, const double* intrinsics,
 int vba_upload_prior(vba_handle h, int window, int n, const double* states_prior, const double* hessian_state) {
     if (int rc = check_window(h, window)) return rc;
     if (int rc_settle = settle(h, true)) return rc_settle;
+    h->touch();
     if (!states_prior || !hessian_state) return fail(VBA_EINVAL, "null prior array");
     if (!h->have_obs[window] && !h->have_win[window]) return fail(VBA_ESTATE, "upload the window before its prior");
     if (n != h->n[window]) return fail(VBA_EINVAL, "the prior needs one row per pose of the window");
@@ -789,15 +831,32 @@ int vba_upload_prior(vba_handle h, int window, int n, const double* states_prior
 int vba_set_prior(vba_handle h, int on) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     h->reg = on != 0;
+    h->touch();
     return VBA_OK;
 }
 
 int vba_set_states(vba_handle h, int window, const double* states, double lamda) {
     if (!h) return fail(VBA_EINVAL, "null handle");
-    if (int rc_settle = settle(h, true)) return rc_settle;
+    VBA_ESTAMP(1);
+    if (int rc_settle = settle(h, true, true)) return rc_settle;        // (states staged earlier are replaced below, or go up first)
     if (!states) return fail(VBA_EINVAL, "null states");
     h->carry_ok = 0;
     double* S = h->S[h->par];           // the input buffer of the next call
+    if (h->h_stage_map && window == 0 && (h->have_obs[0] || h->have_win[0])) {
+        // one-window latency-mode handle: staged only; the first kernel of the next chained schedule takes them from there
+        // (vba_context::h_stage_map).  States staged before and not sent up yet are simply replaced: nothing has been queued
+        // that reads them.
+        if (h->stage_kernel) { HIPCHK(hipSetDevice(h->device)); HIPCHK(hipStreamSynchronize(h->stream)); h->stage_kernel = false; }
+        if (h->stage_copy) { HIPCHK(hipEventSynchronize(h->ev_stage)); h->stage_copy = false; }
+        const int n = h->n[0];
+        std::memcpy(h->h_stage_map, states, (size_t)n * 80);
+        h->h_stage_map[(size_t)n * 10] = lamda;
+        h->pend.on = true; h->pend.par = h->par; h->pend.n = n;
+        h->have_state[0] = 1;
+        VBA_ESTAMP(2);
+        return VBA_OK;
+    }
+    if (int rc = flush_states(h)) return rc;    // (an error return below leaves the earlier states in place, as before)
     if (window == -1) {     // the same states for every window (all windows must have the same number of poses)
         const int n = h->n[0];
         for (int w = 0; w < h->W; ++w) {
@@ -831,6 +890,7 @@ int vba_set_states(vba_handle h, int window, const double* states, double lamda)
     HIPCHK(hipMemcpyAsync(&h->V.sc[window].lam[h->par], h->h_stage + (size_t)h->n_max * 10, 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipEventRecord(h->ev_stage, h->stream));
     h->have_state[window] = 1;
+    VBA_ESTAMP(2);
     return VBA_OK;
 }
 
@@ -954,6 +1014,15 @@ int vba_debug_fetch(vba_handle h, int window, int what, double* out, int64_t cap
     double wmax;
     std::memcpy(&wmax, &sc.wmax_bits[V.par], 8);
     switch (what) {
+#ifdef VBA_ENTRY_STAMPS
+        case 103: {         // diagnostic build: the host stamps around the entry of a chained schedule (vba_context.h): count, ns per interval
+            if (capacity < 12) return fail(VBA_EINVAL, "debug buffer too small");
+            for (int k = 0; k < 6; ++k) { out[2 * k] = g_estamps.cnt[k]; out[2 * k + 1] = g_estamps.sum[k]; }
+            g_estamps = EntryStamps();
+            *count = 12;
+            return VBA_OK;
+        }
+#endif
 #ifdef VBA_RESIDENT_STAMPS
         case 100:           // diagnostic build: the wall-clock stamps of the last k_solve_resident launch (raw 64-bit words)
             return copy(V.cR2 + (size_t)window * V.res_stride * 4, (int64_t)V.res_stride * 4);

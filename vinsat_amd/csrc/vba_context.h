@@ -44,6 +44,25 @@ int fail(int code, const std::string& msg);
             return fail(VBA_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
     } while (0)
 
+// -DVBA_ENTRY_STAMPS (diagnostic build, tools/schedule_gap.py): host wall-clock stamps around the entry of a chained schedule.  Six
+// points form a cycle -- 0 the wait of read_heads has returned, 1 / 2 entry / exit of vba_set_states, 3 entry of vba_run_schedule,
+// 4 / 5 just before / after the launch of the pass's graph -- and interval k (from point k - 1 to point k) is summed whenever the
+// two points were passed one after the other; vba_debug_fetch(what = 103) returns {count, sum in ns} per interval and clears them.
+#ifdef VBA_ENTRY_STAMPS
+struct EntryStamps { int last = -1; double t_last = 0.0; double sum[6] = {}; double cnt[6] = {}; };
+extern EntryStamps g_estamps;
+inline void entry_stamp(int k) {
+    const double now = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    EntryStamps& E = g_estamps;
+    if (E.last == (k + 5) % 6) { E.sum[k] += now - E.t_last; E.cnt[k] += 1.0; }
+    E.last = k;
+    E.t_last = now;
+}
+#define VBA_ESTAMP(k) entry_stamp(k)
+#else
+#define VBA_ESTAMP(k) ((void)0)
+#endif
+
 struct Arena {
     char* base = nullptr;
     size_t size = 0, used = 0;
@@ -98,6 +117,16 @@ struct vba_context {
     int par = 0;                            // parity of the next call (WinScalars: what a call hands on lives in the slots of the reader's parity)
     bool need_hist_reset = false;           // a call was abandoned half way: its histograms may be dirty
     hipEvent_t ev_stage = nullptr;          // the last staged copy has left the staging buffer
+    // One-window latency-mode handles: vba_set_states(window 0) only stages -- states and damping into mapped pinned memory -- and the
+    // first kernel of the next chained schedule (k_reset_calls) copies them into S[par] / sc.lam[par]: no stream copy, no runtime call.
+    // Every other consumer of the states sends them up with the two stream copies first (flush_states, called by settle()).
+    // One buffer is enough: the kernel that reads it has finished when vba_run_schedule returns (read_heads), the copies of a flush
+    // are waited for through ev_stage like those of h_stage.
+    double* h_stage_map = nullptr;          // [n_max * 10 + 2]: states, damping
+    const double* d_stage_map = nullptr;    // ... as the device sees it
+    struct PendingStates { bool on = false; int par = 0, n = 0; } pend;    // staged, not yet on the device: for S[par], n poses
+    bool stage_copy = false;                // copies of a flush may still be reading h_stage_map (ev_stage follows them)
+    bool stage_kernel = false;              // a schedule that was to read h_stage_map did not return cleanly: wait for the stream
     std::vector<int> n, m;
     std::vector<char> have_obs, have_win, have_state, have_prior;
     bool reg = false;               // BA_reg semantics (per-pose prior) for the following calls
@@ -153,8 +182,25 @@ struct vba_context {
     // used first, at most kGraphCache of them (a driver alternates between a handful of schedules: the 20-call loop, its two phases)
     // key: a hash per call's view (the quick reject); views: the bytes of those views, compared exactly on a key match (a 64-bit hash
     // collision would replay another schedule's launches silently; ncalls x sizeof(DevView) of memcmp is ~1 us)
-    struct GraphEntry { std::vector<unsigned long long> key; std::vector<unsigned char> views; hipGraphExec_t exec = nullptr; };
+    // ident: what the handle looked like when key and views were last found equal (graph_ident in vba_schedule.hip) -- a schedule that
+    // finds it unchanged replays without building a single view
+    struct GraphEntry { std::vector<unsigned long long> key, ident; std::vector<unsigned char> views; hipGraphExec_t exec = nullptr; };
     std::vector<GraphEntry> graphs;
+    std::vector<unsigned long long> ident_now;      // (scratch of vba_run_schedule: no allocation per call)
+    // Generation of everything a DevView of view_for_call or a branch of the enqueue functions is made from, apart from what
+    // graph_ident lists itself.  touch() -- called by every entry point that can change one of them -- covers:
+    //   h->V.*          every field of the handle's base view: chunk, chunk2 (vba_set_solver / _solver2), hop, nblk_long
+    //                   (vba_set_integrator, vba_upload_window), acc_lanes, trial_tiles, warm_shift, bucket_cap, jac_f32 (vba_set_option),
+    //                   n_min (vba_upload_observations), m_total, warm_shift (vba_sh_*), inv_sigma2 (Schur add-on)
+    //   h->n, n_long    pose counts (n_min of a view, the count of the staged states) and long edges: the uploads
+    //   h->reg          vba_set_prior
+    //   h->fusion, fusion_auto, chunk_waves, cr_levels, pivot_mode, no_pack, pack_min, warm_enabled, inline_select, carry_enabled,
+    //   pipeline, graph_enabled, cprof.on          vba_set_option, vba_set_solver, vba_sh_run_schedule (fusion)
+    //   h->stream       vba_set_stream (also in the identity itself)
+    // fold_enabled and the VBA_* environment switches are fixed when the handle / the process starts.  A field that is missed here
+    // replays a stale graph: a wrong result, not a slow one.
+    unsigned long long gen = 0;
+    void touch() { ++gen; }
     bool graph_broken = false;              // capture or launch failed once: kernel by kernel from then on
     bool graph_enabled = true;              // vba_set_schedule_graph
     long graph_replays = 0, graph_captures = 0;
@@ -211,7 +257,8 @@ int check_window(vba_handle h, int window);
 int read_heads(vba_handle h);
 const volatile WinHead* head(vba_handle h, int w);
 hipError_t create_aux_stream(hipStream_t* s);
-int settle(vba_handle h, bool boundary = false);
+int settle(vba_handle h, bool boundary = false, bool keep_staged = false);
+int flush_states(vba_handle h);
 int ready(vba_handle h);
 void unpack_scalars(const WinScalars* sc, int par, double* lamda, double* last_hessian, int* n_trials, unsigned* flags);
 

@@ -14,7 +14,7 @@ void launch_select_finish(const DevView& V, hipStream_t s);
 void launch_obs_accumulate(const DevView& V, hipStream_t s);
 void launch_trial(const DevView& V, hipStream_t s);
 void launch_clear_hist(const DevView& V, int which, hipStream_t s);
-void launch_reset_calls(const DevView& V, hipStream_t s);
+void launch_reset_calls(const DevView& V, hipStream_t s, const double* stage = nullptr, int n10 = 0, int clear0 = 0);
 void launch_set_counts(const DevView& V, int w, int n, int m, hipStream_t s);
 void launch_broadcast_states(const DevView& V, int n, double lamda, hipStream_t s);
 void launch_debug_project(const DevView& V, int w, int m, double* est, double* J, double* wt, hipStream_t s);

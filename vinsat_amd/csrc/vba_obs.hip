@@ -21,6 +21,7 @@
 // All of these stream the observation arrays once, coalesced (SoA, 8 B per lane per array); the pose state
 // is gathered through L1/L2 (observations are pose sorted, so a wave touches one or two poses).
 #include "vba_decide.h"
+#include <algorithm>
 #include <cstdlib>
 #include "vba_device.h"
 #include "vba_dyn_body.h"
@@ -1488,12 +1489,28 @@ __global__ void k_set_counts(int* n_arr, int* m_arr, int w, int n, int m) {
     if (m >= 0) m_arr[w] = m;
 }
 
-__global__ void k_reset_calls(DevView V) {
-    const int w = blockIdx.x * 64 + threadIdx.x;
-    if (w < V.W) {
+// The kernel in front of a chain of calls: every window back at call 0.  In front of a chained schedule (vba_run_schedule) it also
+// does what else the entry needs, so that the whole entry is one launch inside the schedule's graph:
+//   stage != nullptr   the states and the damping that vba_set_states left in mapped host memory go into window 0's S[V.par] /
+//                      sc.lam[V.par] (one-window handles; n10 = poses * 10 doubles, an even count: one double2 per thread, the
+//                      caller's exact bits).  The kernels of the call read them behind the kernel boundary.
+//   clear0             the digit-0 histogram of parity V.par is cleared (k_clear_hist, which == 0)
+__global__ __launch_bounds__(256) void k_reset_calls(DevView V, const double* stage, int n10, int clear0) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int stride = gridDim.x * 256;
+    for (int w = t; w < V.W; w += stride) {
         V.sc[w].call_idx = 0;
         V.sc[w].pending = -1;
         V.sc[w].miss = 0;       // (a speculated call that was dropped may have recorded a missed warm select: nobody will repeat it)
+    }
+    if (stage) {
+        const double2* src = reinterpret_cast<const double2*>(stage);
+        double2* dst = reinterpret_cast<double2*>(V.states);
+        for (int k = t; k < n10 / 2; k += stride) dst[k] = src[k];
+        if (t == 0) V.sc[0].lam[V.par] = stage[n10];
+    }
+    if (clear0) {
+        for (int64_t k = t; k < (int64_t)V.W * kSelBins; k += stride) hist0_of(V, (int)(k / kSelBins), V.par)[k % kSelBins] = 0u;
     }
 }
 
@@ -1519,8 +1536,12 @@ void launch_set_counts(const DevView& V, int w, int n, int m, hipStream_t s) {
     hipLaunchKernelGGL(k_set_counts, dim3(1), dim3(1), 0, s, const_cast<int*>(V.n), const_cast<int*>(V.m), w, n, m);
 }
 
-void launch_reset_calls(const DevView& V, hipStream_t s) {
-    hipLaunchKernelGGL(k_reset_calls, dim3((V.W + 63) / 64), dim3(64), 0, s, V);
+void launch_reset_calls(const DevView& V, hipStream_t s, const double* stage, int n10, int clear0) {
+    int64_t items = V.W;
+    if (stage) items = std::max<int64_t>(items, n10 / 2);
+    if (clear0) items = std::max<int64_t>(items, (int64_t)V.W * kSelBins);
+    const int nb = (int)std::min<int64_t>((items + 255) / 256, 1024);       // (grid-stride loops: a longer list is walked)
+    hipLaunchKernelGGL(k_reset_calls, dim3(nb), dim3(256), 0, s, V, stage, n10, clear0);
 }
 
 void launch_broadcast_states(const DevView& V, int n, double lamda, hipStream_t s) {

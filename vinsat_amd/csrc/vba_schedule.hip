@@ -348,7 +348,8 @@ static int finish_stalled_call(vba_handle h, const CallSpec& q, const std::vecto
 // vba_step calls.
 int vba_run_schedule(vba_handle h, int ncalls, const int* iters, const int* inits, int* trials_total) {
     if (!h || !iters || !inits || ncalls < 1) return fail(VBA_EINVAL, "bad argument");
-    if (int rc_settle = settle(h)) return rc_settle;
+    VBA_ESTAMP(3);
+    if (int rc_settle = settle(h, false, true)) return rc_settle;       // (staged states stay staged: the entry kernel takes them)
     if (int rc = ready(h)) return rc;
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
@@ -369,18 +370,21 @@ int vba_run_schedule(vba_handle h, int ncalls, const int* iters, const int* init
         q.fold = fold;
         return q;
     };
-    {
-        DevView V0;
-        view_for_call(h, V0, spec(0, false));
-        if (h->need_hist_reset) {
-            DevView Q = V0;
-            for (int p = 0; p < 2; ++p) { Q.par = p; launch_clear_hist(Q, 1, s); }
-            h->need_hist_reset = false;
-            h->hist_dirty = false;
-        }
-        if (!carry0 && h->hist_dirty) launch_clear_hist(V0, 0, s);
-        launch_reset_calls(V0, s);
+    if (h->need_hist_reset) {
+        DevView Q;
+        view_for_call(h, Q, spec(0, false));
+        for (int p = 0; p < 2; ++p) { Q.par = p; launch_clear_hist(Q, 1, s); }
+        h->need_hist_reset = false;
+        h->hist_dirty = false;
     }
+    // What the entry kernel of the pass (k_reset_calls, the first launch of enqueue_pass) does beside resetting the call counters:
+    // clear the digit-0 histogram that the exact select of call 0 fills (a trial whose states were then replaced may have left a
+    // warm histogram there; cleared whenever call 0 starts without carried keys, dirty or not, so that one graph serves both), and
+    // take the states vba_set_states staged.  Both change what is launched: part of the key and of the identity of a cached graph.
+    const int clear0 = carry0 ? 0 : 1;
+    if (h->pend.on && h->pend.par != par0) { if (int rc = flush_states(h)) return rc; }     // (cannot happen: the parity moves only with a call)
+    const int up_n10 = h->pend.on ? h->pend.n * 10 : 0;
+    if (h->pend.on) { h->pend.on = false; h->stage_kernel = true; }     // from here on the staged states belong to this schedule
     h->hist_dirty = emit_kind != 0;
     for (int w = 0; w < h->W; ++w) { h->h_head[w].call_idx = 0; h->h_head[w].done = 0; h->h_head[w].flags = 0; }
     long trials = 0;
@@ -412,12 +416,26 @@ int vba_run_schedule(vba_handle h, int ncalls, const int* iters, const int* init
         // (... nor with the resident solve of the comparison build, vba_set_fusion bits 5 / 6: its kernels take the epoch of the launch as
         // an argument, which a replay would freeze -- the consumers' flags would read as already set)
         if (!no_graph && h->graph_enabled && guard == 0 && !prof_pass && h->V.lat && !h->graph_broken && next == 0 && (h->fusion & 96) == 0) {
-            gkey.reserve(8 + 3 * (size_t)ncalls);
+            // The identity of the pass: the handle's generation (everything a view or an enqueue function reads that is not listed
+            // here: vba_context::gen) and what this call brings along.  A cached graph whose views were compared byte for byte under
+            // this identity would compare equal again -- nothing they are made from has changed -- so it is replayed without building them.
+            std::vector<unsigned long long>& ident = h->ident_now;
+            ident.clear();
+            ident.push_back(h->gen); ident.push_back((unsigned long long)ncalls); ident.push_back((unsigned long long)par0);
+            ident.push_back((unsigned long long)carry0); ident.push_back((unsigned long long)emit_kind); ident.push_back((unsigned long long)(uintptr_t)s);
+            ident.push_back((unsigned long long)clear0); ident.push_back((unsigned long long)up_n10);
+            for (int c = 0; c < ncalls; ++c) ident.push_back(((unsigned long long)(unsigned)iters[c] << 1) | (inits[c] ? 1ull : 0ull));
+            size_t hit = h->graphs.size();
+            for (size_t k = 0; k < h->graphs.size(); ++k)
+                if (h->graphs[k].ident == ident) { hit = k; break; }
+            if (hit == h->graphs.size()) {      // slow path: the views themselves
+            gkey.reserve(9 + 3 * (size_t)ncalls);
             gviews.resize((size_t)ncalls * sizeof(DevView));
             gkey.push_back((unsigned long long)ncalls); gkey.push_back((unsigned long long)par0); gkey.push_back((unsigned long long)carry0);
             gkey.push_back((unsigned long long)emit_kind); gkey.push_back((unsigned long long)h->pivot_mode);
             gkey.push_back((unsigned long long)h->inline_select | ((unsigned long long)h->fold_enabled << 1));
             gkey.push_back((unsigned long long)(uintptr_t)s);
+            gkey.push_back((unsigned long long)clear0 | ((unsigned long long)up_n10 << 1));
             for (int c = 0; c < ncalls; ++c) {
                 const bool fold = c > 0 && emit_kind == 2 && h->fold_enabled;
                 DevView Vc;
@@ -434,12 +452,15 @@ int vba_run_schedule(vba_handle h, int ncalls, const int* iters, const int* init
                 }
                 gkey.push_back(hsh); gkey.push_back((unsigned long long)iters[c]); gkey.push_back((unsigned long long)inits[c]);
             }
-            size_t hit = h->graphs.size();
             for (size_t k = 0; k < h->graphs.size(); ++k)
-                if (h->graphs[k].key == gkey && h->graphs[k].views == gviews) { hit = k; break; }
+                if (h->graphs[k].key == gkey && h->graphs[k].views == gviews) { hit = k; h->graphs[k].ident = ident; break; }
+            }
             if (hit < h->graphs.size()) {
                 if (hit != 0) std::rotate(h->graphs.begin(), h->graphs.begin() + hit, h->graphs.begin() + hit + 1);     // most recently used first
-                if (hipGraphLaunch(h->graphs[0].exec, s) == hipSuccess) { replayed = true; h->graph_replays++; }
+                VBA_ESTAMP(4);
+                const hipError_t launched = hipGraphLaunch(h->graphs[0].exec, s);
+                VBA_ESTAMP(5);
+                if (launched == hipSuccess) { replayed = true; h->graph_replays++; }
                 else { (void)hipGetLastError(); h->graph_broken = true; }
             } else {
                 if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) capturing = true;
@@ -459,6 +480,11 @@ int vba_run_schedule(vba_handle h, int ncalls, const int* iters, const int* init
         } capture_guard{s, &capturing};
         // speculative part: calls next .. ncalls-1, one trial each
         auto enqueue_pass = [&]() -> int {
+        if (next == 0 && !replayed) {       // the entry kernel: only in front of call 0 (a re-issue from a later call finds the states moved on)
+            DevView V0;
+            view_for_call(h, V0, spec(0, false));
+            launch_reset_calls(V0, s, up_n10 ? h->d_stage_map : nullptr, up_n10, clear0);
+        }
         for (int c = next; c < ncalls && !replayed; ++c) {
             const bool fold = c > next && emit_kind == 2 && h->fold_enabled;       // call c-1 of this pass left its decision to this call's warm select
             const CallSpec q = spec(c, fold);
@@ -511,6 +537,7 @@ int vba_run_schedule(vba_handle h, int ncalls, const int* iters, const int* init
             }
             vba_context::GraphEntry ge;
             ge.key = gkey;
+            ge.ident = h->ident_now;
             ge.views = std::move(gviews);
             ge.exec = exec;
             h->graphs.insert(h->graphs.begin(), std::move(ge));
@@ -519,6 +546,7 @@ int vba_run_schedule(vba_handle h, int ncalls, const int* iters, const int* init
         }
         HIPCHK(hipGetLastError());
         if (int rc = read_heads(h)) return rc;
+        h->stage_kernel = false;        // (the entry kernel has read the staged states)
         trials += (long)(ncalls - next);
         // After a pass over calls next .. ncalls-1 every window whose counter is below ncalls is stalled AT that call.
         // Every stalled call is finished with the ordinary LM loop -- each one, not only the earliest: a window left at a
@@ -577,6 +605,7 @@ int vba_run_schedule(vba_handle h, int ncalls, const int* iters, const int* init
 int vba_set_schedule_graph(vba_handle h, int on) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc = settle(h)) return rc;
+    h->touch();
     h->graph_enabled = on != 0;
     return VBA_OK;
 }
@@ -591,6 +620,7 @@ int vba_schedule_graph_stats(vba_handle h, int* captures, int* replays) {
 int vba_set_chain_profile(vba_handle h, int on) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc = settle(h)) return rc;
+    h->touch();
     h->cprof.on = on != 0;
     return VBA_OK;
 }
@@ -747,6 +777,7 @@ static bool can_pipeline(vba_handle h) {
 static int iterate_pipelined(vba_handle h, int iter, int initialize, double* states_out, double* lamda_out, double* last_hessian,
                              int* n_trials, unsigned* flags) {
     if (int rc = ready(h)) return rc;
+    if (int rc = flush_states(h)) return rc;        // (vba_iterate_open: the states it staged go up in front of the call)
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     constexpr int emit_kind = 2;

@@ -23,6 +23,7 @@ static void sharded_view(vba_handle h, DevView& V) {
 int vba_sh_stage1(vba_handle h, int iter, int initialize, int64_t m_total, double* d_abs_local) {
     if (!h || !d_abs_local || m_total < 1) return fail(VBA_EINVAL, "bad argument");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (h->W != 1) return fail(VBA_EINVAL, "sharded mode uses a single window per handle");
     if (h->reg) return fail(VBA_EINVAL, "sharded mode does not take a prior (vba_set_prior)");
     if (int rc = ready(h)) return rc;
@@ -150,6 +151,7 @@ int vba_sh_unique_id(const char* rccl_path, void* id128) {
 int vba_sh_comm_init(vba_handle h, const char* rccl_path, const void* id128, int nranks, int rank) {
     if (!h || !rccl_path || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(VBA_EINVAL, "bad argument");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (h->W != 1) return fail(VBA_EINVAL, "sharded mode uses a single window per handle");
     if (h->shc.comm) return fail(VBA_ESTATE, "the handle has a communicator already");
     h->sharded = true;
@@ -236,6 +238,7 @@ int sh_ensure_buffers(vba_handle h, int64_t m_total) {
         const int shift = keys <= 300000 ? 44 : (keys <= 600000 ? 43 : 42);
         if (h->V.warm_shift != shift) {
             h->V.warm_shift = shift;
+            h->touch();
             h->carry_ok = 0;
             S.carried = false;
         }
@@ -429,6 +432,7 @@ struct Sh2 {
 int vba_sh_set_protocol(vba_handle h, int carried_keys) {
     if (!h) return fail(VBA_EINVAL, "null handle");
     if (int rc = settle(h)) return rc;
+    h->touch();
     h->shc.protocol = carried_keys ? 1 : 0;
     h->shc.carried = false;
     return VBA_OK;
@@ -448,6 +452,7 @@ int vba_sh_run_schedule(vba_handle h, int ncalls, const int* iters, const int* i
     auto& S = h->shc;
     if (!S.comm) return fail(VBA_ESTATE, "vba_sh_comm_init has not run");
     if (int rc_settle = settle(h)) return rc_settle;
+    h->touch();
     if (h->W != 1) return fail(VBA_EINVAL, "sharded mode uses a single window per handle");
     if (h->reg) return fail(VBA_EINVAL, "sharded mode does not take a prior (vba_set_prior)");
     if (int rc = ready(h)) return rc;
