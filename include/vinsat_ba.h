@@ -401,6 +401,53 @@ int vba_outlier_power(vba_handle h, int iter, int damped, double ncp, double cri
 /* HIP-event time of the last vba_outlier_power on the handle's stream (front + inversion + row pass + window totals), milliseconds. */
 int vba_last_outlier_power_ms(vba_handle h, float* ms);
 
+/* ---- data snooping (Baarda): ACT on the w-test.  Per pose, the observation row whose w-test exceeds a critical value by most is
+ * rejected ON THE DEVICE: its confidence in the device observation block becomes 0, its original value and a mask byte are kept.
+ * Without it the only way to reject a row is to zero its confidence on the host and call vba_upload_observations again, which
+ * packs and uploads every row of the window.
+ * System and w-test: exactly the system of vba_reliability(h, iter, damped, ...) at the RESIDENT states; wtest of every row has the
+ * bits vba_reliability would return at that moment (the same row pass with the same mapping, csrc/vba_rowpass.h).
+ *   crit > 0   the critical value, in wtest's own units: a caller who wants a quantile of the normal distribution passes
+ *              quantile * s0 (s0 of vba_outlier_power); +inf rejects nothing;
+ *   candidates of pose i: its rows with current weight w_k > 0, wtest finite and wtest > crit.  A row whose wtest is NaN is never
+ *              rejected;
+ *   cnt_i      the pose's rows of non-zero weight;
+ *   mode 0     snooping: the candidate with the largest wtest is rejected -- ties go to the smallest input row index -- and only
+ *              if cnt_i - 1 >= min_rows;
+ *   mode 1     every flagged row: all candidates of the pose are rejected if cnt_i - #candidates >= min_rows; otherwise the rule
+ *              of mode 0 applies to that pose;
+ *   min_rows >= 0  the rows of non-zero weight a pose keeps at least;
+ *   a window the covariance step flagged VBA_FLAG_ZERO_PIVOT, VBA_FLAG_NONFINITE or VBA_FLAG_INDEFINITE rejects nothing;
+ *   rejected [W][m_max]  bytes, 1 = rejected, in the INPUT order of the rows, CUMULATIVE over the calls since the window's rows
+ *              were uploaded; the whole array is written, bytes beyond a window's m are 0;
+ *   counts [W][2]  rows rejected by this call, rows rejected in total;
+ *   flags [W]  the flags of the covariance step (see vba_covariance).
+ * A rejected row STAYS in the window with weight zero, exactly as the reference treats a row of confidence 0: it still counts in
+ * the median of |r| (BA_filtering.py:23) and in m, the divisor of the residual means.  Nothing is compacted.
+ * The promise: from the call's return on the handle gives, bit for bit, what a handle would give on which
+ * vba_upload_observations had been called with those confidences zeroed and the same states and lamda set -- calls, schedules,
+ * graph replays and all three queries.  So the call is a boundary as an upload is: carried keys are dropped, a speculated call of
+ * the pipelined loop is dropped, schedule graphs are matched again; states, lamda and flags are untouched and the permutation
+ * stays valid -- also when nothing is rejected.
+ * vba_snoop_restore puts the original confidences of `window` (-1: every window) back and clears its mask, a boundary of the
+ * same kind.  vba_upload_observations of a window clears that window's mask: those are new rows.  vba_get_rejected returns the
+ * cumulative mask (as `rejected` above) and the totals [W]; either may be NULL.
+ * VBA_EINVAL: crit not positive or NaN, mode not 0 / 1, min_rows < 0.  VBA_ESTATE before every window has states, and on
+ * observation-sharded handles.  Scratch beyond the reliability query's (allocated too: its wtest array and its index per row are
+ * used) is allocated by the first vba_snoop: a double and a byte per observation row and window, an int per pose; VBA_ENOMEM if
+ * that fails.  Synchronous; only the non-NULL outputs are copied to the host.
+ * Algorithm: the shadow front and the selected inversion of vba_covariance, then ONE launch (csrc/vba_snoop.hip): the row pass of
+ * vba_reliability, a segmented arg-max per pose by a butterfly of fixed shape, and the stores of the lanes that own rejected
+ * rows.  No atomics; equal settings give equal bits; a window has the same result alone and in a batch. */
+int vba_snoop(vba_handle h, int iter, int damped, double crit, int mode, int min_rows,
+              unsigned char* rejected /*[W][m_max], input order, cumulative; or NULL*/,
+              int* counts /*[W][2]: rejected by this call, rejected in total; or NULL*/,
+              unsigned* flags /*[W] or NULL*/);
+int vba_snoop_restore(vba_handle h, int window /* -1: every window */);
+int vba_get_rejected(vba_handle h, unsigned char* rejected /*[W][m_max]*/, int* totals /*[W]*/);
+/* HIP-event time of the last vba_snoop on the handle's stream (front + inversion + the snooping launch), milliseconds. */
+int vba_last_snoop_ms(vba_handle h, float* ms);
+
 /* Timing of the last vba_step measured with HIP events on the handle's stream, milliseconds. */
 int vba_last_step_ms(vba_handle h, float* ms);
 

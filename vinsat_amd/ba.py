@@ -772,6 +772,52 @@ def outlier_power(iter=None, damped=False, ncp=17.075, crit=None):
 outlier_power.last = {}
 
 
+def snoop(iter=None, damped=False, crit=3.29, scaled=True, mode=0, min_rows=6):
+    """Data snooping at the states the last :func:`BA` / :func:`BA_reg` / :func:`BA_window` call returned (``vba_snoop``,
+    ``include/vinsat_ba.h``): per pose, the row whose w-test (:func:`reliability`'s) exceeds the critical value by most is rejected
+    on the device -- ``mode=1``: every row above it -- as long as the pose keeps ``min_rows`` rows of non-zero weight.  A rejected
+    row stays in the window with confidence 0, as if the rows had been passed in so.  ``iter``, ``damped`` and the prior as in
+    :func:`covariance`.  ``scaled``: ``crit`` is a quantile of the standard normal distribution (3.29: a 0.1 % test) and is
+    multiplied by ``s0`` of :func:`outlier_power`, taken first; a NaN ``s0`` raises, and so does a batch (one critical value per
+    call: pass ``scaled=False`` and ``crit`` in the units of ``wtest`` there).
+
+    Returns the cumulative mask of rejected rows shaped as :func:`reliability`'s arrays (bool).  ``snoop.last``: ``counts``
+    (``[rejected by this call, in total]`` per window), ``flags`` and the ``crit`` that was used.
+
+    Lifetime: the rejections live on the device until the rows are uploaded again.  A following ``BA`` call with unchanged
+    arguments keeps them (and, fed the states the last call returned, stays resident); :func:`invalidate`, changed rows or
+    another window lose them.  :func:`rejected` reads them back, :func:`restore_rejected` undoes them."""
+    used = float(crit)
+    if scaled:
+        fit = outlier_power(iter=iter, damped=damped)[-1]
+        if isinstance(fit, list):
+            raise ValueError("snoop(scaled=True) takes one window: a batch has one s0 per window and a call one critical value")
+        if not fit.s0 == fit.s0:
+            raise RuntimeError("snoop(scaled=True): s0 of the fit is NaN (no redundancy, or a window without a covariance)")
+        used = float(crit) * fit.s0
+    eng, (rej, counts, flags), ns, form = _query("snoop", lambda eng, it: eng.snoop(it, used, mode=mode, min_rows=min_rows, damped=damped),
+                                                 iter)
+    ms = [int(eng.m[b]) for b in range(len(ns))]
+    cn = [[int(x) for x in counts[b]] for b in range(len(ns))]
+    fl = [int(x) for x in flags[:len(ns)]]
+    snoop.last = dict(counts=cn[0] if form == "single" else cn, flags=fl[0] if form == "single" else fl, crit=used)
+    return _shaped(rej, ms, form)
+
+
+snoop.last = {}
+
+
+def rejected():
+    """The rows :func:`snoop` has rejected since the window's rows were uploaded, shaped as :func:`reliability`'s arrays (bool)."""
+    eng, (rej, _), ns, form = _query("rejected", lambda eng, it: eng.rejected(), None)
+    return _shaped(rej, [int(eng.m[b]) for b in range(len(ns))], form)
+
+
+def restore_rejected():
+    """Undo every rejection of :func:`snoop` on the engine of the last call: the rows get their confidences back."""
+    _query("restore_rejected", lambda eng, it: eng.snoop_restore(-1), None)
+
+
 def scaled_sigmas(cov, fit):
     """:func:`pose_sigmas` of ``cov`` times ``s0`` of ``fit`` (:func:`outlier_power`): 1-sigma values in km, km/s and rad under the
     a-posteriori variance factor of the observation class.  ``fit``: one record, or a list of records -- one per window of a

@@ -426,7 +426,7 @@ int vba_destroy(vba_handle h) {
     if (h->h_back) hipHostFree(h->h_back);
     if (h->h_head) hipHostFree(h->h_head);
     if (h->d_dbg) hipFree(h->d_dbg);
-    for (QueryScratch* q : {&h->q_cov, &h->q_rel, &h->q_pow}) {
+    for (QueryScratch* q : {&h->q_cov, &h->q_rel, &h->q_pow, &h->q_snoop}) {
         if (q->d) hipFree(q->d);
         if (q->ev) hipEventDestroy(q->ev);
     }
@@ -702,6 +702,7 @@ int vba_upload_observations(vba_handle h, int window, int n, int64_t m, const do
     std::vector<int64_t>& perm = h->perm[window];
     perm.assign(m, 0);
     if (!h->perm_stale.empty()) h->perm_stale[window] = 1;
+    if (!h->snoop_total.empty()) if (int rc = snoop_forget_window(h, window)) return rc;    // new rows: nothing of them is rejected
     {
         std::vector<int> cur(ptr.begin(), ptr.end() - 1);
         for (int64_t k = 0; k < m; ++k) perm[cur[ii[k]]++] = k;

@@ -7,6 +7,7 @@
 //   vba_cov.hip          per-pose marginal covariances (vba_covariance); the step and the scaffold the three queries share
 //   vba_rel.hip          per-row leverages and w-tests (vba_reliability)
 //   vba_power.hip        per-row detectable biases and influences, the fit's variance factor (vba_outlier_power)
+//   vba_snoop.hip        data snooping: rows rejected by their w-test on the device (vba_snoop)
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -213,6 +214,10 @@ struct vba_context {
     QueryScratch q_cov;                      // the shadow of every array the front of a call writes, Sigma's blocks (cov_layout)
     QueryScratch q_rel;                      // rel_layout: the two row arrays, the device copy of perm, the pose summary
     QueryScratch q_pow;                      // pow_layout: four row arrays, the pose and window summaries
+    // Data snooping (vba_snoop.hip).  Its scratch is state, not a query's: the confidences the rejected rows had and the cumulative
+    // mask (snoop_layout), allocated by the first vba_snoop.  snoop_total: rows rejected per window (empty until then)
+    QueryScratch q_snoop;
+    std::vector<int> snoop_total;
     hipEvent_t cov_ev0 = nullptr;
     bool sharded = false;                   // an observation-sharded call has run (vba_sh_*): no covariance query
     std::vector<char> perm_stale;           // [W] once a row pass has run: the device copy of perm[w] predates the last upload
@@ -334,5 +339,10 @@ int query_last_ms(vba_handle h, QueryScratch vba_context::*q, float* ms, const c
 // input row, [W][m_max], part of the reliability scratch, uploaded for the windows whose rows changed), and the copy of a
 // per-window result to the host (`used[w] * per` doubles of every window's `stride`; the rest stays as the caller left it).
 int rel_device_perm(vba_handle h, const int** d_perm);
+int rel_device_bufs(vba_handle h, RelBufs& b);
 int query_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per);
+
+// ---- vba_snoop.hip
+// vba_upload_observations of a window whose handle has snooped: the window's mask is cleared (its rows are new ones)
+int snoop_forget_window(vba_handle h, int window);
 #pragma GCC visibility pop

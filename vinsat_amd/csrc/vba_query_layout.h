@@ -1,4 +1,4 @@
-// vba_query_layout.h -- how the scratch of a query (vba_covariance, vba_reliability, vba_outlier_power) is cut into buffers.
+// vba_query_layout.h -- how the scratch of a query (vba_covariance, vba_reliability, vba_outlier_power, vba_snoop) is cut into buffers.
 // Plain host C++ without HIP, so that tests/hostcheck/sanitize_power_main.cpp runs it under the sanitizers.
 //
 // A layout is written once, as a function that takes its buffers from a Carver in order; it runs twice: over a Carver without a
@@ -40,5 +40,17 @@ inline PowBufs pow_layout(Carver& c, size_t W, size_t N, size_t M) {
     b.pfit = c.take<double>(W * N * 4);
     b.paux = c.take<double>(W * N * 2);
     b.fit = c.take<double>(W * 8);
+    return b;
+}
+
+// vba_snoop, beyond the reliability scratch (whose wtest array and device copy of the permutation it uses).  Unlike a query's, this
+// scratch is state: orig [W][m_max] the confidence a rejected row had, mask [W][m_max] the cumulative rejections, both in the input
+// order of the rows and valid until the window's rows are uploaded again; prej [W][n_max] rows each pose lost in the last call.
+struct SnoopBufs { double* orig; unsigned char* mask; int* prej; };
+inline SnoopBufs snoop_layout(Carver& c, size_t W, size_t N, size_t M) {
+    SnoopBufs b;
+    b.orig = c.take<double>(W * M);
+    b.mask = c.take<unsigned char>(W * M);
+    b.prej = c.take<int>(W * N);
     return b;
 }

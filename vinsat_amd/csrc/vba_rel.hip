@@ -131,6 +131,12 @@ int rel_device_perm(vba_handle h, const int** d_perm) {
     return VBA_OK;
 }
 
+// ... and the whole scratch with it: what vba_snoop (vba_snoop.hip) takes -- it stores its w-tests where k_reliability does.
+int rel_device_bufs(vba_handle h, RelBufs& b) {
+    if (int rc = rel_reserve(h, b)) return rc;
+    return rel_upload_perm(h, b.perm);
+}
+
 int vba_reliability(vba_handle h, int iter, int damped, double* leverage, double* wtest, double* pose_stats, unsigned* flags) {
     if (int rc = cov_begin(h, iter, "vba_reliability")) return rc;
     RelBufs b;

@@ -344,6 +344,37 @@ class BAEngine:
     def last_outlier_power_ms(self):
         return self._last_ms("outlier_power")
 
+    def snoop(self, it, crit, mode=0, min_rows=6, damped=False):
+        """``vba_snoop``: data snooping on the device.  Per pose, the row whose w-test (:meth:`reliability`'s, at the resident
+        states) exceeds ``crit`` by most is rejected -- ``mode=1``: every row above ``crit`` -- as long as the pose keeps
+        ``min_rows`` rows of non-zero weight: its confidence on the device becomes 0, as if the rows had been uploaded so
+        (``include/vinsat_ba.h`` carries the rule and the promise).  ``crit`` is in the units of ``wtest``.
+
+        Returns ``(rejected [W, m_max] bool, cumulative, input order; counts [W, 2]: by this call, in total; flags [W])``."""
+        W = self.windows
+        rej = np.zeros((W, self.m_max), dtype=np.uint8)
+        counts = np.zeros((W, 2), dtype=np.int32)
+        flags = np.empty(W, dtype=np.uint32)
+        _lib.check(self.lib.vba_snoop(self.h, int(it), int(bool(damped)), float(crit), int(mode), int(min_rows), rej.ctypes.data,
+                                      counts.ctypes.data_as(ctypes.POINTER(c_int)), flags.ctypes.data_as(ctypes.POINTER(c_uint))),
+                   self.lib)
+        return rej.astype(bool), counts, flags
+
+    def snoop_restore(self, window=-1):
+        """``vba_snoop_restore``: the rejected rows of ``window`` (-1: every window) get their confidences back."""
+        _lib.check(self.lib.vba_snoop_restore(self.h, int(window)), self.lib)
+
+    def rejected(self):
+        """``vba_get_rejected``: ``(rejected [W, m_max] bool in input order, totals [W])`` since the rows were uploaded."""
+        W = self.windows
+        rej = np.zeros((W, self.m_max), dtype=np.uint8)
+        tot = np.zeros(W, dtype=np.int32)
+        _lib.check(self.lib.vba_get_rejected(self.h, rej.ctypes.data, tot.ctypes.data_as(ctypes.POINTER(c_int))), self.lib)
+        return rej.astype(bool), tot
+
+    def last_snoop_ms(self):
+        return self._last_ms("snoop")
+
     def debug(self, what, window=0):
         n, m = self.n[window], self.m[window]
         shapes = dict(est=(m, 2), weight=(m,), H=(n, 6, 6), b=(n, 6), Phi=(n, 6, 6), r_pred=(n - 1, 7), qgrad=(n, 3),

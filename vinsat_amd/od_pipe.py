@@ -334,6 +334,16 @@ class SequenceRun:
             self.errors.append((prop[:, :3] - self.poses_gt[t_init:t, :3]).norm(dim=-1))
             self.times.append(time_idx[-prop.shape[0]:])
 
+    def reject(self, rows):
+        """Rows of the sequence (input order) that the following batches see with confidence 0: what data snooping rejected in
+        a batch (:func:`streaming_version`, ``snoop=``).  The run's confidences are replaced by a private copy; the arrays of the
+        window the run was made from, and the slices handed out by ``next_patch`` so far, stay as they are."""
+        rows = np.asarray(rows, dtype=np.int64)
+        if rows.size:
+            conf = self.conf.clone()
+            conf[rows] = 0.0
+            self.conf = conf
+
     def result(self):
         import torch
         return torch.cat(self.errors), self.first_detection, self.times
@@ -402,7 +412,7 @@ class _Clock:
 
 def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, detections_file_name=None,
                       ba=None, num_iters=NUM_ITERS, record=None, timing=None, run=None, device=0, covariances=None,
-                      reliability=None):
+                      reliability=None, snoop=None, snoop_log=None):
     """Drop-in for the reference's ``streaming_version`` (od_pipe.py:911-1062).
 
     ``ba`` defaults to the HIP-backed :func:`vinsat_amd.ba.BA`; tests may inject another
@@ -417,9 +427,20 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
     ``reliability`` (a list) receives, after every batch, ``dict(leverage, wtest)`` of that batch's rows in their input order
     (:func:`vinsat_amd.ba.reliability`, ``[m]`` each) under the same two conditions.  Nothing is rejected on them here: the
     outlier mask of the data preparation stays the ground-truth one of the reference.
+    ``snoop`` (``None``: nothing changes): ``dict(crit=3.29, rounds=3, calls=4, mode=0, min_rows=6, scaled=True)``, any key
+    optional -- data snooping behind the calls of every batch (:func:`vinsat_amd.ba.snoop`, default ``ba`` only).  At most
+    ``rounds`` rounds: a round rejects rows on the device and, if it rejected any, is followed by ``calls`` more full-phase
+    resident calls (``iter = num_iters - 1``); a round that rejects nothing ends the loop.  The rows rejected in a batch keep
+    confidence 0 in the later batches of the sequence (a private copy of the run's confidences, :meth:`SequenceRun.reject`; the
+    caller's arrays are never edited) -- which is what the device held.  ``snoop_log`` (a list) receives per batch the rejected
+    input rows (an int64 array).
     """
     if covariances is not None and ba is not None:
         raise ValueError("covariances needs the default (HIP) ba")
+    if snoop is not None and ba is not None:
+        raise ValueError("snoop needs the default (HIP) ba")
+    if snoop is not None:
+        snoop = dict(dict(crit=3.29, rounds=3, calls=4, mode=0, min_rows=6, scaled=True), **snoop)
     if reliability is not None and ba is not None:
         raise ValueError("reliability needs the default (HIP) ba")
     ba_window = None
@@ -461,6 +482,21 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
             lev, wt = _reliability()
             reliability.append(dict(leverage=lev[0].clone(), wtest=wt[0].clone()))
             t0 = clk("bookkeeping", t0)
+        if snoop is not None:
+            from . import ba as _ba
+            for _ in range(int(snoop["rounds"])):
+                _ba.snoop(crit=snoop["crit"], scaled=snoop["scaled"], mode=snoop["mode"], min_rows=snoop["min_rows"])
+                if _ba.snoop.last["counts"][0] == 0:
+                    break
+                if snoop["calls"] > 0:
+                    more = int(snoop["calls"])
+                    states_t, vel_t, lam, last_h = _ba.BA_window([num_iters - 1] * more, [False] * more, states_t, vel_t, p["imu"],
+                                                                 p["uv"], p["xyz"], p["ii"], p["time_idx"], p["intr"], p["conf"], lam)
+            rows = np.nonzero(_ba.rejected()[0].numpy())[0].astype(np.int64)
+            run.reject(rows)
+            if snoop_log is not None:
+                snoop_log.append(rows)
+            t0 = clk("ba", t0)
         run.finish_patch(states_t, vel_t)
     out = run.result()
     clk("bookkeeping", t0)
@@ -468,7 +504,7 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
 
 
 def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=None, timing=None, threads=None, device=0, covariances=None,
-                      reliability=None):
+                      reliability=None, snoop=None):
     """Many sequences at once -- the reference's outer loop over sequence files (od_pipe.py:1069-1077) turned into the batch
     dimension of ``BA``: round r runs batch r of EVERY sequence that still has one as the windows of ONE ragged handle
     (:func:`vinsat_amd.ba.BA_window` on lists: every kernel launch covers all of them), sequences that have ended drop out.
@@ -480,8 +516,10 @@ def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=Non
     marginal covariance ``[9, 9]`` of the last pose of that sequence's batch (:func:`vinsat_amd.ba.covariance`); it needs the
     default ``ba_window`` and changes no result.  ``reliability`` (a list) receives ``dict(round, sequence, leverage, wtest)`` after
     every round: the values of that sequence's batch rows in their input order (:func:`vinsat_amd.ba.reliability`), under the same
-    conditions.
+    conditions.  ``snoop`` (:func:`streaming_version`) is not served here: the scaled critical value is one per window.
     """
+    if snoop is not None:
+        raise NotImplementedError("streaming_batched does not snoop: run the sequences through streaming_version(snoop=...)")
     if covariances is not None and ba_window is not None:
         raise ValueError("covariances needs the default (HIP) ba_window")
     if reliability is not None and ba_window is not None:
