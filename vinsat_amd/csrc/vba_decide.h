@@ -3,7 +3,7 @@
 // Two callers evaluate it with the same arithmetic (fixed-order sums over the same block partials, so the same bits):
 //   * k_decide (vba_solve.hip): its own launch, one block per window -- every trial of a call-by-call step, the later
 //     trials of any call, the last call of a chained schedule;
-//   * the first kernel of the NEXT call of a chained schedule (k_select_warm, vba_obs.hip): every block of that kernel
+//   * the first kernel of the NEXT call of a chained schedule (k_select_warm, vba_select.hip): every block of that kernel
 //     re-evaluates the test of the call in front of it in its prologue and simply goes on if the first trial was accepted
 //     -- the kernel boundary, the launch and the single-block tail of a separate decide kernel are gone from the chain.
 //     A trial that is not cleanly accepted (rejected, pivot check failed, non-finite) leaves everything untouched: the
