@@ -445,8 +445,40 @@ int vba_snoop(vba_handle h, int iter, int damped, double crit, int mode, int min
               unsigned* flags /*[W] or NULL*/);
 int vba_snoop_restore(vba_handle h, int window /* -1: every window */);
 int vba_get_rejected(vba_handle h, unsigned char* rejected /*[W][m_max]*/, int* totals /*[W]*/);
-/* HIP-event time of the last vba_snoop on the handle's stream (front + inversion + the snooping launch), milliseconds. */
+/* HIP-event time of the last vba_snoop or vba_snoop_scaled on the handle's stream (front + inversion + the snooping launches),
+ * milliseconds. */
 int vba_last_snoop_ms(vba_handle h, float* ms);
+
+/* ---- scaled data snooping: vba_snoop with a critical value PER WINDOW, quantile * s0 of the window's own fit, formed on the
+ * device behind ONE covariance step.  A quantile of the normal distribution compares with wtest / s0 (see vba_outlier_power),
+ * and s0 is one number per window: with vba_snoop a caller needs vba_outlier_power, a host multiply and one vba_snoop per
+ * distinct critical value -- two covariance steps for one window, W + 1 for a batch.
+ * For window w:
+ *   s0sq [W]       the variance factor of the observation class at the resident states: the bits of fit[w][4] that
+ *                  vba_outlier_power(h, iter, damped, ...) would return at that moment;
+ *   crit_used [W]  quantile * sqrt(s0sq[w]): the IEEE double product of the correctly rounded square root (what
+ *                  numpy.float64(quantile) * numpy.sqrt(s0sq) gives on the host).  NaN if s0sq[w] is NaN or not > 0 -- a window
+ *                  without redundancy, without Sigma, or with every confidence zero -- and such a window rejects nothing;
+ *   candidates, mode, min_rows, the tie rule, barred windows, rejected, counts, flags and the kept confidences are exactly those
+ *                  of vba_snoop at crit = crit_used[w].
+ * The contract in one sentence: for every window the handle ends in the state, with the mask and the counts, that
+ * vba_outlier_power, a host multiply and vba_snoop(crit_used[w]) would leave on a handle that holds only that window -- bit for
+ * bit, whatever the batch.
+ * The promise and the boundary behaviour are vba_snoop's, also when nothing is rejected; vba_snoop_restore, vba_get_rejected and
+ * vba_upload_observations treat the mask as they do after vba_snoop, and calls of the two may be mixed.
+ * VBA_EINVAL: quantile not positive or NaN (+inf rejects nothing), mode not 0 / 1, min_rows < 0.  VBA_ESTATE before every window
+ * has states, and on observation-sharded handles.  Scratch beyond vba_snoop's: three doubles per pose and two per window,
+ * allocated by the first call; VBA_ENOMEM if that fails.  Synchronous; only the non-NULL outputs are copied to the host;
+ * vba_last_snoop_ms reports this call as well.
+ * Algorithm: the shadow front and the selected inversion of vba_covariance once, then three launches (csrc/vba_snoop.hip): the row
+ * pass of vba_snoop, which stores every wtest and, per pose, the sums vba_outlier_power's row pass forms (in its order and with
+ * its rounding); one wavefront per window for the totals, in the order of vba_outlier_power's, s0sq and the critical value; and a
+ * pass over the stored wtests with vba_snoop's butterfly, decision and stores.  No atomics; equal settings give equal bits; a
+ * window has the same result alone and in a batch. */
+int vba_snoop_scaled(vba_handle h, int iter, int damped, double quantile, int mode, int min_rows,
+                     unsigned char* rejected /*[W][m_max], input order, cumulative; or NULL*/,
+                     int* counts /*[W][2]: rejected by this call, rejected in total; or NULL*/,
+                     double* crit_used /*[W] or NULL*/, double* s0sq /*[W] or NULL*/, unsigned* flags /*[W] or NULL*/);
 
 /* Timing of the last vba_step measured with HIP events on the handle's stream, milliseconds. */
 int vba_last_step_ms(vba_handle h, float* ms);

@@ -59,6 +59,7 @@ SIGNATURES = {
     "vba_outlier_power": (c_int, [c_void_p, c_int, c_int, c_double, c_double, PD, PD, PD, PD, PD, PD, POINTER(c_uint)]),
     "vba_last_outlier_power_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_snoop": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_void_p, POINTER(c_int), POINTER(c_uint)]),
+    "vba_snoop_scaled": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_void_p, POINTER(c_int), PD, PD, POINTER(c_uint)]),
     "vba_snoop_restore": (c_int, [c_void_p, c_int]),
     "vba_get_rejected": (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
     "vba_last_snoop_ms": (c_int, [c_void_p, POINTER(c_float)]),

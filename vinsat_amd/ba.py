@@ -807,6 +807,37 @@ def snoop(iter=None, damped=False, crit=3.29, scaled=True, mode=0, min_rows=6):
 snoop.last = {}
 
 
+def snoop_scaled(iter=None, damped=False, quantile=3.29, mode=0, min_rows=6):
+    """:func:`snoop` with ``scaled=True`` in one device call, for one window, a dense batch or a ragged list
+    (``vba_snoop_scaled``, ``include/vinsat_ba.h``): every window is tested against ``quantile * s0`` of its own fit (``s0`` of
+    :func:`outlier_power`), formed on the device behind one covariance step.  The rule, ``mode``, ``min_rows``, ``iter``,
+    ``damped``, the prior and the lifetime of the rejections are :func:`snoop`'s; per window the result is, bit for bit, that of
+    ``snoop(crit=quantile, scaled=True)`` on that window alone.
+
+    Returns the cumulative mask of rejected rows shaped as :func:`reliability`'s arrays (bool).  ``snoop_scaled.last``:
+    ``counts`` (``[rejected by this call, in total]``), ``flags``, ``crit`` (the critical value used) and ``s0`` -- scalars for
+    one window, lists per window for a batch.  A window whose ``s0`` is NaN (no redundancy, no covariance, every confidence zero)
+    rejects nothing: for one window that raises, as :func:`snoop` does; in a batch it shows in ``last`` (``crit`` and ``s0`` NaN)."""
+    eng, (rej, counts, crit, s0sq, flags), ns, form = _query(
+        "snoop_scaled", lambda eng, it: eng.snoop_scaled(it, quantile, mode=mode, min_rows=min_rows, damped=damped), iter)
+    B = len(ns)
+    ms = [int(eng.m[b]) for b in range(B)]
+    cn = [[int(x) for x in counts[b]] for b in range(B)]
+    fl = [int(x) for x in flags[:B]]
+    cr = [float(x) for x in crit[:B]]
+    s0 = [float(np.sqrt(x)) if x >= 0 else float("nan") for x in s0sq[:B]]
+    single = form == "single"
+    snoop_scaled.last = dict(counts=cn[0] if single else cn, flags=fl[0] if single else fl, crit=cr[0] if single else cr,
+                             s0=s0[0] if single else s0)
+    if single and not cr[0] == cr[0]:
+        raise RuntimeError("snoop_scaled(): s0 of the fit is NaN or zero (no redundancy, or a window without a covariance): "
+                           "nothing was rejected")
+    return _shaped(rej, ms, form)
+
+
+snoop_scaled.last = {}
+
+
 def rejected():
     """The rows :func:`snoop` has rejected since the window's rows were uploaded, shaped as :func:`reliability`'s arrays (bool)."""
     eng, (rej, _), ns, form = _query("rejected", lambda eng, it: eng.rejected(), None)

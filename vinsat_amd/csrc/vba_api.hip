@@ -426,7 +426,7 @@ int vba_destroy(vba_handle h) {
     if (h->h_back) hipHostFree(h->h_back);
     if (h->h_head) hipHostFree(h->h_head);
     if (h->d_dbg) hipFree(h->d_dbg);
-    for (QueryScratch* q : {&h->q_cov, &h->q_rel, &h->q_pow, &h->q_snoop}) {
+    for (QueryScratch* q : {&h->q_cov, &h->q_rel, &h->q_pow, &h->q_snoop, &h->q_snoop_fit}) {
         if (q->d) hipFree(q->d);
         if (q->ev) hipEventDestroy(q->ev);
     }

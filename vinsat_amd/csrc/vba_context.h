@@ -7,7 +7,7 @@
 //   vba_cov.hip          per-pose marginal covariances (vba_covariance); the step and the scaffold the three queries share
 //   vba_rel.hip          per-row leverages and w-tests (vba_reliability)
 //   vba_power.hip        per-row detectable biases and influences, the fit's variance factor (vba_outlier_power)
-//   vba_snoop.hip        data snooping: rows rejected by their w-test on the device (vba_snoop)
+//   vba_snoop.hip        data snooping: rows rejected by their w-test on the device (vba_snoop, vba_snoop_scaled)
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -218,6 +218,7 @@ struct vba_context {
     // mask (snoop_layout), allocated by the first vba_snoop.  snoop_total: rows rejected per window (empty until then)
     QueryScratch q_snoop;
     std::vector<int> snoop_total;
+    QueryScratch q_snoop_fit;                // vba_snoop_scaled's own scratch, a query's (snoop_fit_layout): nothing in it outlives a call
     hipEvent_t cov_ev0 = nullptr;
     bool sharded = false;                   // an observation-sharded call has run (vba_sh_*): no covariance query
     std::vector<char> perm_stale;           // [W] once a row pass has run: the device copy of perm[w] predates the last upload

@@ -1,5 +1,6 @@
-// vba_query_layout.h -- how the scratch of a query (vba_covariance, vba_reliability, vba_outlier_power, vba_snoop) is cut into buffers.
-// Plain host C++ without HIP, so that tests/hostcheck/sanitize_power_main.cpp runs it under the sanitizers.
+// vba_query_layout.h -- how the scratch of a query (vba_covariance, vba_reliability, vba_outlier_power, vba_snoop,
+// vba_snoop_scaled) is cut into buffers.  Plain host C++ without HIP, so that tests/hostcheck/sanitize_power_main.cpp and
+// sanitize_snoop_fit_main.cpp run it under the sanitizers.
 //
 // A layout is written once, as a function that takes its buffers from a Carver in order; it runs twice: over a Carver without a
 // base it only counts (total() is the size to allocate), over the allocation it places the buffers.  Every buffer starts on a
@@ -52,5 +53,15 @@ inline SnoopBufs snoop_layout(Carver& c, size_t W, size_t N, size_t M) {
     b.orig = c.take<double>(W * M);
     b.mask = c.take<unsigned char>(W * M);
     b.prej = c.take<int>(W * N);
+    return b;
+}
+
+// vba_snoop_scaled, beside the snoop state above and a query's scratch like the first three: pose [W][n_max][3] per pose the sum
+// of w |r|^2, the sum of the leverages and the rows of non-zero weight; win [W][2] per window s0sq and the critical value used.
+struct SnoopFitBufs { double *pose, *win; };
+inline SnoopFitBufs snoop_fit_layout(Carver& c, size_t W, size_t N) {
+    SnoopFitBufs b;
+    b.pose = c.take<double>(W * N * 3);
+    b.win = c.take<double>(W * 2);
     return b;
 }

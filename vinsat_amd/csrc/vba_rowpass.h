@@ -54,9 +54,10 @@ __device__ __forceinline__ Row row_take(const DevView& V, const RowGroup& g, int
     return o;
 }
 
-// The group of this thread and its first row.  False for a block beyond the window's poses (block uniform).
-__device__ __forceinline__ bool rowpass_begin(const DevView& V, const double* __restrict__ diag, const unsigned* __restrict__ flags,
-                                              const int* __restrict__ perm, RowGroup& g, Row& nxt) {
+// The mapping alone: the group of this thread, its rows and the window's scalars -- all a pass needs that reads stored row
+// results and no Sigma (k_snoop_pick, vba_snoop.hip); pc and S stay unset.  False for a block beyond the window's poses.
+__device__ __forceinline__ bool rowpass_rows(const DevView& V, const unsigned* __restrict__ flags, const int* __restrict__ perm,
+                                             RowGroup& g) {
     const int w = blockIdx.y;
     const int n = V.n[w];
     g.m = V.m[w];
@@ -73,6 +74,13 @@ __device__ __forceinline__ bool rowpass_begin(const DevView& V, const double* __
     g.no_sigma = (flags[w] & (VBA_FLAG_ZERO_PIVOT | VBA_FLAG_NONFINITE)) != 0u;
     g.inv_wmax = 1.0 / bits_f64(V.sc[w].wmax_bits[V.par]);
     g.pw = perm + g.mb;
+    return true;
+}
+
+// The group of this thread and its first row.  False for a block beyond the window's poses (block uniform).
+__device__ __forceinline__ bool rowpass_begin(const DevView& V, const double* __restrict__ diag, const unsigned* __restrict__ flags,
+                                              const int* __restrict__ perm, RowGroup& g, Row& nxt) {
+    if (!rowpass_rows(V, flags, perm, g)) return false;
     // the first row is requested before the pose's camera and covariance block: independent round trips side by side
     nxt = Row{};
     if (g.beg + g.sub < g.end) nxt = row_load(V, g, g.beg + g.sub);

@@ -360,6 +360,23 @@ class BAEngine:
                    self.lib)
         return rej.astype(bool), counts, flags
 
+    def snoop_scaled(self, it, quantile, mode=0, min_rows=6, damped=False):
+        """``vba_snoop_scaled``: :meth:`snoop` with one critical value per window, ``quantile * s0`` of the window's own fit
+        (``s0sq`` of :meth:`outlier_power`), formed on the device behind one covariance step.  A window whose ``s0sq`` is NaN or
+        not positive rejects nothing and reports a NaN critical value.
+
+        Returns ``(rejected [W, m_max] bool, cumulative, input order; counts [W, 2]; crit_used [W]; s0sq [W]; flags [W])``."""
+        W = self.windows
+        rej = np.zeros((W, self.m_max), dtype=np.uint8)
+        counts = np.zeros((W, 2), dtype=np.int32)
+        crit = np.empty(W)
+        s0sq = np.empty(W)
+        flags = np.empty(W, dtype=np.uint32)
+        _lib.check(self.lib.vba_snoop_scaled(self.h, int(it), int(bool(damped)), float(quantile), int(mode), int(min_rows),
+                                             rej.ctypes.data, counts.ctypes.data_as(ctypes.POINTER(c_int)), _p(crit), _p(s0sq),
+                                             flags.ctypes.data_as(ctypes.POINTER(c_uint))), self.lib)
+        return rej.astype(bool), counts, crit, s0sq, flags
+
     def snoop_restore(self, window=-1):
         """``vba_snoop_restore``: the rejected rows of ``window`` (-1: every window) get their confidences back."""
         _lib.check(self.lib.vba_snoop_restore(self.h, int(window)), self.lib)

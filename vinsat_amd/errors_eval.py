@@ -50,14 +50,16 @@ def _resolve(ba):
     return getattr(importlib.import_module(mod), attr)
 
 
-def _run_share(pairs, ba, batched, timing=None):
+def _run_share(pairs, ba, batched, timing=None, snoop_each=None):
     """The sequences of ``pairs`` through the driver on the current device; returns (errors, times) per sequence."""
     from .od_pipe import prepared_runs, streaming_batched, streaming_version
     if batched:
         if ba is not None:
             raise ValueError("batched=True drives vinsat_amd.ba.BA_window itself")
-        results = streaming_batched(list(pairs), timing=timing) if pairs else []       # (files are read by the preparing threads)
+        results = streaming_batched(list(pairs), timing=timing, snoop_each=snoop_each) if pairs else []     # (files are read by the preparing threads)
     else:
+        if snoop_each is not None:
+            raise ValueError("snoop_each needs batched=True (one sequence at a time: streaming_version(snoop=...))")
         # the next sequences are read and prepared on host threads while this one's BA calls run (`prep` in the timing is then
         # what the consumer still waited for)
         import time
@@ -90,7 +92,7 @@ def split_longest_first(sizes, workers):
     return [sorted(s_) for s_ in share]
 
 
-def _run_replicas(pairs, devices, ba, batched, configure, timeout):
+def _run_replicas(pairs, devices, ba, batched, configure, timeout, snoop_each=None):
     """One fresh worker process per entry of ``devices`` (the reference's outer loop over sequence files, od_pipe.py:1069-1077, is
     embarrassingly parallel: SURVEY.md 8(e) "the shape that does scale").  THIS process does not touch a GPU for it: every worker is
     started as a child (`python -m vinsat_amd.errors_eval --worker job.json`) with HIP_VISIBLE_DEVICES narrowed to its device
@@ -119,7 +121,7 @@ def _run_replicas(pairs, devices, ba, batched, configure, timeout):
                 procs.append(None)
                 continue
             job = dict(pairs=[pairs[k] for k in idx], ba=ba if (ba is None or isinstance(ba, str)) else None, batched=bool(batched),
-                       configure=configure or {}, out=os.path.join(tmp, f"w{w}.pkl"))
+                       configure=configure or {}, snoop_each=snoop_each, out=os.path.join(tmp, f"w{w}.pkl"))
             with open(os.path.join(tmp, f"w{w}.json"), "w") as f:
                 json.dump(job, f)
             env = dict(os.environ, HIP_VISIBLE_DEVICES=str(visible[dev] if visible else dev),
@@ -176,19 +178,23 @@ def _worker(job_path):
         ba_mod.configure(**{k: (tuple(v) if isinstance(v, list) else v) for k, v in job["configure"].items()})
     timing = {}
     t0 = time.perf_counter()
-    errors, times = _run_share([tuple(p) for p in job["pairs"]], _resolve(job["ba"]), job["batched"], timing=timing)
+    errors, times = _run_share([tuple(p) for p in job["pairs"]], _resolve(job["ba"]), job["batched"], timing=timing,
+                               snoop_each=job.get("snoop_each"))
     timing["wall"] = time.perf_counter() - t0
     with open(job["out"], "wb") as f:
         pickle.dump(dict(errors=errors, times=times, timing=timing), f)
 
 
-def run_folder(folder, ba=None, batched=False, gpus=None, workers_per_gpu=1, configure=None, timeout=3600.0, stats=None):
+def run_folder(folder, ba=None, batched=False, gpus=None, workers_per_gpu=1, configure=None, timeout=3600.0, stats=None,
+               snoop_each=None):
     """Process every ``*_all_detections.npy`` / ``*_orbit_eci_zyxvecs.npy`` pair under ``folder`` (the layout of
     od_pipe.py:1064-1075: ``tmp_dets/`` and ``tmp_pose/``) and save errors.npy / times.npy next to them.
 
     ``batched=True``: the sequences are the batch dimension of ``BA`` -- every sequence's current batch is a window of ONE
     ragged handle and each kernel launch covers all of them (:func:`vinsat_amd.od_pipe.streaming_batched`) -- instead of
-    one sequence after the other as the reference's loop (od_pipe.py:1069-1077) runs them.
+    one sequence after the other as the reference's loop (od_pipe.py:1069-1077) runs them.  ``snoop_each`` (a dict, with
+    ``batched=True`` only) is passed through to it: scaled data snooping of every window against its own ``s0`` behind the
+    calls of every round.
 
     ``gpus``: None = this process, its current device.  An int N (devices 0 .. N-1) or a list of device indices (a device may be
     named more than once) = REPLICAS: the sequences are dealt longest-first to ``len(gpus) * workers_per_gpu`` fresh worker
@@ -205,7 +211,7 @@ def run_folder(folder, ba=None, batched=False, gpus=None, workers_per_gpu=1, con
             from . import ba as ba_mod
             ba_mod.configure(**configure)
         timing = {}
-        errors, times = _run_share(pairs, _resolve(ba), batched, timing=timing)
+        errors, times = _run_share(pairs, _resolve(ba), batched, timing=timing, snoop_each=snoop_each)
         if stats is not None:
             stats.append(dict(worker=0, device=None, sequences=len(pairs), **timing))
     else:
@@ -215,7 +221,7 @@ def run_folder(folder, ba=None, batched=False, gpus=None, workers_per_gpu=1, con
         if ba is not None and not isinstance(ba, str):
             raise ValueError("with gpus=..., ba must be None or a 'module:attribute' string (it is imported in the worker processes)")
         devices = [d for d in devices for _ in range(workers_per_gpu)]
-        errors, times, st = _run_replicas(pairs, devices, ba, batched, configure, timeout)
+        errors, times, st = _run_replicas(pairs, devices, ba, batched, configure, timeout, snoop_each=snoop_each)
         if stats is not None:
             stats.extend(st)
     save_results(folder, errors, times)

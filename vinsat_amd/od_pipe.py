@@ -410,6 +410,11 @@ class _Clock:
         return self.now()
 
 
+def _check_until(until):
+    if until not in ("clean", "rounds"):
+        raise ValueError('until must be "clean" (stop after a round that rejects nothing) or "rounds" (run every round)')
+
+
 def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, detections_file_name=None,
                       ba=None, num_iters=NUM_ITERS, record=None, timing=None, run=None, device=0, covariances=None,
                       reliability=None, snoop=None, snoop_log=None):
@@ -427,10 +432,12 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
     ``reliability`` (a list) receives, after every batch, ``dict(leverage, wtest)`` of that batch's rows in their input order
     (:func:`vinsat_amd.ba.reliability`, ``[m]`` each) under the same two conditions.  Nothing is rejected on them here: the
     outlier mask of the data preparation stays the ground-truth one of the reference.
-    ``snoop`` (``None``: nothing changes): ``dict(crit=3.29, rounds=3, calls=4, mode=0, min_rows=6, scaled=True)``, any key
-    optional -- data snooping behind the calls of every batch (:func:`vinsat_amd.ba.snoop`, default ``ba`` only).  At most
-    ``rounds`` rounds: a round rejects rows on the device and, if it rejected any, is followed by ``calls`` more full-phase
-    resident calls (``iter = num_iters - 1``); a round that rejects nothing ends the loop.  The rows rejected in a batch keep
+    ``snoop`` (``None``: nothing changes): ``dict(crit=3.29, rounds=3, calls=4, mode=0, min_rows=6, scaled=True,
+    until="clean")``, any key optional -- data snooping behind the calls of every batch (:func:`vinsat_amd.ba.snoop`, default
+    ``ba`` only).  At most ``rounds`` rounds: a round rejects rows on the device and, if it rejected any, is followed by
+    ``calls`` more full-phase resident calls (``iter = num_iters - 1``); a round that rejects nothing ends the loop.  With
+    ``until="rounds"`` every one of the ``rounds`` rounds runs and is followed by its ``calls`` calls, whatever it rejected
+    (the rounds :func:`streaming_batched` runs with ``snoop_each``, where the other windows decide).  The rows rejected in a batch keep
     confidence 0 in the later batches of the sequence (a private copy of the run's confidences, :meth:`SequenceRun.reject`; the
     caller's arrays are never edited) -- which is what the device held.  ``snoop_log`` (a list) receives per batch the rejected
     input rows (an int64 array).
@@ -440,7 +447,8 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
     if snoop is not None and ba is not None:
         raise ValueError("snoop needs the default (HIP) ba")
     if snoop is not None:
-        snoop = dict(dict(crit=3.29, rounds=3, calls=4, mode=0, min_rows=6, scaled=True), **snoop)
+        snoop = dict(dict(crit=3.29, rounds=3, calls=4, mode=0, min_rows=6, scaled=True, until="clean"), **snoop)
+        _check_until(snoop["until"])
     if reliability is not None and ba is not None:
         raise ValueError("reliability needs the default (HIP) ba")
     ba_window = None
@@ -486,7 +494,7 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
             from . import ba as _ba
             for _ in range(int(snoop["rounds"])):
                 _ba.snoop(crit=snoop["crit"], scaled=snoop["scaled"], mode=snoop["mode"], min_rows=snoop["min_rows"])
-                if _ba.snoop.last["counts"][0] == 0:
+                if snoop["until"] == "clean" and _ba.snoop.last["counts"][0] == 0:
                     break
                 if snoop["calls"] > 0:
                     more = int(snoop["calls"])
@@ -504,7 +512,7 @@ def streaming_version(detections=None, orbit_np=None, orbit_file_name=None, dete
 
 
 def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=None, timing=None, threads=None, device=0, covariances=None,
-                      reliability=None, snoop=None):
+                      reliability=None, snoop=None, snoop_each=None, snoop_log=None):
     """Many sequences at once -- the reference's outer loop over sequence files (od_pipe.py:1069-1077) turned into the batch
     dimension of ``BA``: round r runs batch r of EVERY sequence that still has one as the windows of ONE ragged handle
     (:func:`vinsat_amd.ba.BA_window` on lists: every kernel launch covers all of them), sequences that have ended drop out.
@@ -517,9 +525,22 @@ def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=Non
     default ``ba_window`` and changes no result.  ``reliability`` (a list) receives ``dict(round, sequence, leverage, wtest)`` after
     every round: the values of that sequence's batch rows in their input order (:func:`vinsat_amd.ba.reliability`), under the same
     conditions.  ``snoop`` (:func:`streaming_version`) is not served here: the scaled critical value is one per window.
+    ``snoop_each`` (``None``: nothing changes) is: ``dict(crit=3.29, rounds=3, calls=4, mode=0, min_rows=6, until="clean")``, any
+    key optional -- scaled data snooping behind the calls of every round, every live window against ``crit`` (a quantile) times
+    its own ``s0`` in one device call (:func:`vinsat_amd.ba.snoop_scaled`).  At most ``rounds`` snooping rounds: one in which
+    any window rejected a row is followed by ``calls`` more full-phase resident ``BA_window`` calls (``iter = num_iters - 1``) on
+    the same lists; with ``until="clean"`` a round in which no window rejected anything ends the loop, with ``until="rounds"``
+    every round runs and is followed by its calls.  A sequence's rejected rows keep confidence 0 in its later batches
+    (:meth:`SequenceRun.reject`); ``snoop_log`` (a list) receives ``dict(round, sequence, rows)`` per round and sequence, ``rows``
+    the rejected input rows (an int64 array).  A sequence gets the bits of its own
+    ``streaming_version(snoop=dict(scaled=True, ...))`` run where the two run the same rounds (``until="rounds"`` in both).
     """
     if snoop is not None:
-        raise NotImplementedError("streaming_batched does not snoop: run the sequences through streaming_version(snoop=...)")
+        raise NotImplementedError("streaming_batched does not take snoop=: pass snoop_each=dict(...), the scaled snooping of every "
+                                  "window against its own s0, or run the sequences through streaming_version(snoop=...)")
+    if snoop_each is not None:
+        snoop_each = dict(dict(crit=3.29, rounds=3, calls=4, mode=0, min_rows=6, until="clean"), **snoop_each)
+        _check_until(snoop_each["until"])
     if covariances is not None and ba_window is not None:
         raise ValueError("covariances needs the default (HIP) ba_window")
     if reliability is not None and ba_window is not None:
@@ -556,6 +577,34 @@ def streaming_batched(sequences, num_iters=NUM_ITERS, ba_window=None, record=Non
                                       [p["time_idx"] for p in ps], [p["intr"] for p in ps], [p["conf"] for p in ps],
                                       [p["lam"] for p in ps])
         t0 = clk("ba", t0, num_iters * len(ps))
+        if snoop_each is not None:
+            from . import ba as _ba
+            masks = None
+            more = int(snoop_each["calls"])
+            for _ in range(int(snoop_each["rounds"])):
+                # (a single window left without an s0 raises here, as streaming_version's ba.snoop does; in a batch it rejects nothing)
+                masks = _ba.snoop_scaled(quantile=snoop_each["crit"], mode=snoop_each["mode"], min_rows=snoop_each["min_rows"])
+                counts = _ba.snoop_scaled.last["counts"]
+                now = counts[0] if len(ps) == 1 else sum(c[0] for c in counts)
+                if snoop_each["until"] == "clean" and now == 0:
+                    break
+                if more > 0 and len(ps) == 1:
+                    p = ps[0]
+                    s1, _, l1, _ = ba_window([num_iters - 1] * more, [False] * more, st[0], p["velocities"], p["imu"], p["uv"],
+                                             p["xyz"], p["ii"], p["time_idx"], p["intr"], p["conf"], lam[0])
+                    st, lam = [s1], [l1]
+                elif more > 0:
+                    st, _, lam, _ = ba_window([num_iters - 1] * more, [False] * more, st, [p["velocities"] for p in ps],
+                                              [p["imu"] for p in ps], [p["uv"] for p in ps], [p["xyz"] for p in ps],
+                                              [p["ii"] for p in ps], [p["time_idx"] for p in ps], [p["intr"] for p in ps],
+                                              [p["conf"] for p in ps], lam)
+            for b, (k, r, _) in enumerate(live):
+                mask = np.zeros(0, dtype=bool) if masks is None else np.asarray(masks[b]).reshape(-1)
+                rows = np.nonzero(mask)[0].astype(np.int64)
+                r.reject(rows)
+                if snoop_log is not None:
+                    snoop_log.append(dict(round=rnd, sequence=k, rows=rows))
+            t0 = clk("ba", t0)
         if covariances is not None:
             from .ba import covariance
             cov = covariance()
