@@ -623,6 +623,28 @@ int vba_schur_last_info(vba_schur_handle h, int* info);
 int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, float* solve_ms);
 /* what = 0: the step of the last iterate [6 n + 3 L]; 1: its Cholesky factor, dense lower triangular [6n, 6n] */
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity);
+/* Covariances of the free-landmark system at the resident state: blocks of the inverse of H = [[B, E], [E^T, C]] as
+ * vba_schur_iterate(h, lamda, ...) would build it there (lamda on every diagonal entry of B and C; lamda = 0, the usual
+ * case, gives the undamped covariance -- the catalogue prior fixes the gauge).  With S = B - E C^-1 E^T and Y_k = E_k C_l^-1:
+ *   pose_cov[i] = (S^-1)_ii: the marginal of pose i over all landmarks and all other poses, coordinates [dp (km), dtheta]
+ *                 (dtheta as in vba_covariance: the attitude sigma is 2 sqrt(.)); one triangle computed and mirrored;
+ *   pair_cov[b] = (S^-1)_{blk_i[b], blk_j[b]} for every block of the uploaded block list (i >= j, diagonal blocks included,
+ *                 bitwise the blocks of pose_cov): the cross-covariances of poses that share a landmark;
+ *   lm_cov[l]   = C_l^-1 + sum over the rows k, k' of l of Y_k^T (S^-1)_{pose(k), pose(k')} Y_k', exactly symmetric.  For a
+ *                 landmark without rows: d I with d = 1.0 / (1.0 / (sigma_prior * sigma_prior) + lamda), each of the three
+ *                 operations rounded to double in that order, and exact zeros off the diagonal.
+ * Any output may be NULL.  The weights are the confidences as uploaded, so -- as for vba_covariance -- this is a covariance up
+ * to the variance factor of the weights.  *info is as vba_schur_last_info reports it for an iterate at this damping: 0, or 1 +
+ * the first row with a non-positive pivot; then every requested output is filled with NaN and the call still returns VBA_OK.
+ * VBA_EINVAL: null handle, null info, lamda negative or NaN (or uploaded pair lists that do not enumerate the row pairs of
+ * every landmark); VBA_ESTATE: before upload or before a state is set; VBA_ENOMEM: no room for the scratch.
+ * The query changes nothing: it builds and factorises into scratch of its own (allocated by the first query of a handle; a
+ * handle that never asks allocates none).  State, last_info, last_ms and debug_fetch read as before, and the following
+ * iterates return the bits they would have returned without it.  Fixed order of operations: equal bits for equal problems. */
+int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov /*[n][6][6] or NULL*/, double* pair_cov /*[nblk][6][6] or NULL*/,
+                         double* lm_cov /*[L][3][3] or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_covariance on this handle (build, factorisation, selected inverse and gathers) */
+int vba_schur_last_covariance_ms(vba_schur_handle h, float* ms);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,11 @@
 //   k_trsv_step     one tile step of the forward / backward substitution (stored inverse diagonal factors), a launch per step
 //   k_lm_update     dl, new landmarks, new poses (retraction as BA_filtering.py:56-60)
 //   k_cost          sum w |r|^2 + prior, block partials
+// Covariance query (vba_schur_covariance: build and factor into scratch of its own, then)
+//   k_trinv_step    W = Lg^-1 on the matrix cores, a launch per tile distance from the diagonal, products beyond the band skipped
+//   k_syrk_wtw      S^-1 = W^T W on the matrix cores, block per tile of the lower triangle
+//   k_cov_gather    the listed 6x6 blocks of S^-1 (pair_cov) and its diagonal blocks (pose_cov)
+//   k_lm_cov        thread per landmark: C_l^-1 + sum Y_k^T Sigma_{pose(k), pose(k')} Y_k'
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -681,6 +686,190 @@ __global__ __launch_bounds__(256) void k_cost(SchurView V, const double* states,
     if (threadIdx.x == 0) V.part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// ------------------------------------------------------------------------------------------------ covariance query
+// vba_schur_covariance: S^-1 = W^T W with W = Lg^-1, over the nbu = ceil(N / kT) tiles that hold unknowns (the tiles of nothing
+// but padding are never touched; inside the last used tile the padding rows of W are rows of the identity and meet the columns
+// < N with exact zeros).  W and the result are [Npad][Npad] row major like S, lower tile triangle.
+//
+// acc += op(A) B for 64x64 tiles staged in LDS, in the fragment layout of k_gemm_abt (wave quadrant r0 / c0, lane lr / lk):
+// TA = false reads A[r][k], TA = true reads A[k][r] (A^T B); B is read as B[k][c].
+template <bool TA>
+__device__ __forceinline__ void tile_mma(vf4 (&acc)[2][2], const double (*As)[kT + 1], const double (*Bs)[kT + 1], int r0, int c0, int lr, int lk) {
+#pragma unroll 4
+    for (int s = 0; s < kT / 4; ++s) {
+        const int k = 4 * s + lk;
+        const double a0 = TA ? As[k][r0 + lr] : As[r0 + lr][k], a1 = TA ? As[k][r0 + 16 + lr] : As[r0 + 16 + lr][k];
+        const double b0 = Bs[k][c0 + lr], b1 = Bs[k][c0 + 16 + lr];
+        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+}
+
+__device__ __forceinline__ void tile_stage(double (*Ts)[kT + 1], const double* src, size_t ld, int t) {
+    for (int e = t; e < kT * kT; e += 256) Ts[e / kT][e % kT] = src[(size_t)(e / kT) * ld + e % kT];
+}
+
+// The tiles at distance d below the diagonal of W = Lg^-1, a launch per distance (every tile of a launch reads tiles of smaller
+// distances only): W_JJ = invL_J,  W_IJ = -invL_I sum_{K = max(J, I - bw)}^{I - 1} L_IK W_KJ  for I = J + d; block J.  The factor
+// of a banded matrix keeps its band, so L_IK = 0 for I - K > bw and those products are skipped (as k_trsv_step skips them); W
+// itself is full below the diagonal.  K runs upwards: one fixed order.
+__global__ __launch_bounds__(256) void k_trinv_step(SchurView V, double* W, int d, int bw) {
+    __shared__ double As[kT][kT + 1];
+    __shared__ double Bs[kT][kT + 1];
+    const int t = threadIdx.x, J = blockIdx.x, I = J + d;
+    const size_t ld = (size_t)V.Npad;
+    double* Wij = W + (size_t)(I * kT) * ld + (size_t)J * kT;
+    if (d == 0) {
+        const double* Li = V.invL + (size_t)J * kT * kT;
+        for (int e = t; e < kT * kT; e += 256) Wij[(size_t)(e / kT) * ld + e % kT] = Li[e];
+        return;
+    }
+    const int lane = t & 63, wv = t >> 6, r0 = (wv >> 1) * 32, c0 = (wv & 1) * 32, lr = lane & 15, lk = lane >> 4;
+    vf4 acc[2][2], out[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y] = out[x][y] = (vf4){0.0, 0.0, 0.0, 0.0};
+    for (int K = max(J, I - bw); K < I; ++K) {
+        tile_stage(As, V.S + (size_t)(I * kT) * ld + (size_t)K * kT, ld, t);
+        tile_stage(Bs, W + (size_t)(K * kT) * ld + (size_t)J * kT, ld, t);
+        __syncthreads();
+        tile_mma<false>(acc, As, Bs, r0, c0, lr, lk);
+        __syncthreads();
+    }
+    tile_stage(As, V.invL + (size_t)I * kT * kT, kT, t);
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Bs[r0 + 16 * x + lk + 4 * i][c0 + 16 * y + lr] = acc[x][y][i];
+    __syncthreads();
+    tile_mma<false>(out, As, Bs, r0, c0, lr, lk);
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Wij[(size_t)(r0 + 16 * x + lk + 4 * i) * ld + c0 + 16 * y + lr] = -out[x][y][i];
+}
+
+// Tile (I, J), I >= J, of S^-1 = W^T W:  sum_{K = I}^{nbu - 1} W_KI^T W_KJ  (W_KI = 0 above the diagonal), K upwards, one block per
+// tile of the lower triangle (enumerated as k_gemm_abt<1> does); diagonal tiles are stored whole.  out may be the array the factor
+// lived in: W is all this kernel reads.
+__global__ __launch_bounds__(256) void k_syrk_wtw(SchurView V, const double* W, double* out, int nbu) {
+    __shared__ double As[kT][kT + 1];
+    __shared__ double Bs[kT][kT + 1];
+    const int t = threadIdx.x, q = blockIdx.x;
+    int I = (int)((sqrt(8.0 * q + 1.0) - 1.0) * 0.5);
+    while ((I + 1) * (I + 2) / 2 <= q) ++I;
+    while (I * (I + 1) / 2 > q) --I;
+    const int J = q - I * (I + 1) / 2;
+    const size_t ld = (size_t)V.Npad;
+    const int lane = t & 63, wv = t >> 6, r0 = (wv >> 1) * 32, c0 = (wv & 1) * 32, lr = lane & 15, lk = lane >> 4;
+    vf4 acc[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y] = (vf4){0.0, 0.0, 0.0, 0.0};
+    for (int K = I; K < nbu; ++K) {
+        tile_stage(As, W + (size_t)(K * kT) * ld + (size_t)I * kT, ld, t);
+        tile_stage(Bs, W + (size_t)(K * kT) * ld + (size_t)J * kT, ld, t);
+        __syncthreads();
+        tile_mma<true>(acc, As, Bs, r0, c0, lr, lk);
+        __syncthreads();
+    }
+    double* Cp = out + (size_t)(I * kT) * ld + (size_t)J * kT;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Cp[(size_t)(r0 + 16 * x + lk + 4 * i) * ld + c0 + 16 * y + lr] = acc[x][y][i];
+}
+
+// The listed 6x6 blocks (i >= j) of S^-1 in block-list order, thread per entry; a diagonal block is read from its lower triangle
+// and mirrored, and goes to pose[i] as well (the same values: bitwise equal).
+__global__ __launch_bounds__(256) void k_cov_gather(SchurView V, const double* Sinv, double* pair, double* pose) {
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= (int64_t)V.nblk * 36) return;
+    const int b = (int)(id / 36), e = (int)(id % 36), a = e / 6, c = e % 6;
+    const int i = V.blk_i[b], j = V.blk_j[b];
+    const int r = i == j ? 6 * i + max(a, c) : 6 * i + a, cc = i == j ? 6 * i + min(a, c) : 6 * j + c;
+    const double v = Sinv[(size_t)r * V.Npad + cc];
+    pair[id] = v;
+    if (i == j) pose[(size_t)i * 36 + e] = v;
+}
+
+// Landmark marginals, thread per landmark:  C_l^-1 + sum over the row pairs (k >= k') of l of  T (k = k')  or  T + T^T (k > k'),
+// T = Y_k^T Sigma_{pose(k), pose(k')} Y_k',  in the order k upwards, k' upwards inside; lp_blk (CSR lp_ptr over the landmarks,
+// pairs in that order) names the gathered block of each pair.  The upper triangle is summed and mirrored.  A landmark without
+// rows gets 1 / (inv_sigma2 + lamda) on its diagonal (one division) and exact zeros beside it.
+__global__ __launch_bounds__(256) void k_lm_cov(SchurView V, const double* pair, const int* lp_ptr, const int* lp_blk, double* lm) {
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= V.L) return;
+    const int beg = V.lm_ptr[l], end = V.lm_ptr[l + 1];
+    double o[6];                    // 00, 01, 02, 11, 12, 22
+    if (beg == end) {
+        const double d = 1.0 / (V.inv_sigma2 + V.lamda);
+        o[0] = o[3] = o[5] = d;
+        o[1] = o[2] = o[4] = 0.0;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 6; ++e) o[e] = V.Cinv[(size_t)l * 6 + e];
+        int slot = lp_ptr[l];
+        for (int k = beg; k < end; ++k) {
+            const double* Yk = V.Y + (size_t)k * 18;
+            for (int k2 = beg; k2 <= k; ++k2, ++slot) {
+                const double* Sg = pair + (size_t)lp_blk[slot] * 36;
+                const double* Y2 = V.Y + (size_t)k2 * 18;
+                double M[6][3], T[3][3];
+#pragma unroll
+                for (int p = 0; p < 6; ++p)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) s = fma(Sg[6 * p + q], Y2[3 * q + c], s);
+                        M[p][c] = s;
+                    }
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int p = 0; p < 6; ++p) s = fma(Yk[3 * p + r], M[p][c], s);
+                        T[r][c] = s;
+                    }
+                int e = 0;
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = r; c < 3; ++c) { o[e] += k2 == k ? T[r][c] : T[r][c] + T[c][r]; ++e; }
+            }
+        }
+    }
+    double* out = lm + (size_t)l * 9;
+    out[0] = o[0]; out[1] = o[1]; out[2] = o[2];
+    out[3] = o[1]; out[4] = o[3]; out[5] = o[4];
+    out[6] = o[2]; out[7] = o[4]; out[8] = o[5];
+}
+
+// Scratch of vba_schur_covariance, allocated by the first query of a handle: every array the build and the factorisation write,
+// W, the gathered blocks and the landmarks' pair -> block index (built on the host from the uploaded lists, once per upload).
+struct SchurQuery {
+    char* arena = nullptr;
+    double *Cinv = nullptr, *wl = nullptr, *E = nullptr, *Y = nullptr, *S = nullptr, *g = nullptr, *ybuf = nullptr, *invL = nullptr, *dl = nullptr;
+    double *W = nullptr, *pair = nullptr, *pose = nullptr, *lm = nullptr;
+    int *info = nullptr, *lp_ptr = nullptr, *lp_blk = nullptr;
+    hipEvent_t ev[2] = {};
+    bool indexed = false;
+    float ms = 0.0f;
+};
+
 thread_local std::string g_serr;
 int sfail(int code, const std::string& msg) { g_serr = msg; return code; }
 
@@ -710,6 +899,7 @@ struct vba_schur_context {
     bool uploaded = false, have_state = false;
     float ms[4] = {0, 0, 0, 0};
     int64_t npairs = 0;
+    SchurQuery q;               // vba_schur_covariance's scratch (nothing until the first query)
     int bw = 1 << 30;           // tile bandwidth of the reduced system (max |I - J| over its non-zero tiles), from the block list
 };
 
@@ -778,6 +968,8 @@ int vba_schur_destroy(vba_schur_handle h) {
     if (h->ev_chain) hipEventDestroy(h->ev_chain);
     if (h->ev_bulk) hipEventDestroy(h->ev_bulk);
     for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : h->q.ev) if (e) hipEventDestroy(e);
+    if (h->q.arena) hipFree(h->q.arena);
     if (h->arena) hipFree(h->arena);
     delete h;
     return VBA_OK;
@@ -819,6 +1011,7 @@ int vba_schur_upload(vba_schur_handle h, const int* lm_ptr, const int* row_pose,
     h->V.inv_sigma2 = 1.0 / (sigma_prior * sigma_prior);
     h->bw = 0;
     for (int b = 0; b < V.nblk; ++b) h->bw = std::max(h->bw, (6 * blk_i[b] + 5) / kT - (6 * blk_j[b]) / kT);
+    h->q.indexed = false;
     h->uploaded = true;
     return VBA_OK;
 }
@@ -855,28 +1048,21 @@ static int schur_cost(vba_schur_handle h, const double* states, const double* X,
     return VBA_OK;
 }
 
-int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, double* cost_after, int* accepted) {
-    if (!h || !cost_before || !cost_after || !accepted) return sfail(VBA_EINVAL, "null argument");
-    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
-    SCHK(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    SchurView V = h->V;
-    V.lamda = lamda;
-    V.states = h->S0; V.X = h->X0buf; V.states_new = h->S1; V.X_new = h->X1buf;
-    if (int rc = schur_cost(h, V.states, V.X, cost_before)) return rc;
-    SCHK(hipEventRecord(h->ev[0], s));
+// Build the reduced camera system of the view's state and damping and factorise it, on stream s (the bulk of a panel's trailing
+// update beside it on h->aux): S, g, Cinv, wl, E, Y, invL and *d_info are the view's and the caller's, so vba_schur_iterate runs it
+// on the handle's arrays and vba_schur_covariance on scratch of its own.  ev_built (if given) is recorded between the two parts.
+static int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built) {
     SCHK(hipMemsetAsync(V.S, 0, (size_t)V.Npad * V.Npad * 8, s));
     SCHK(hipMemsetAsync(V.g, 0, (size_t)V.Npad * 8, s));
-    SCHK(hipMemsetAsync(h->d_info, 0, 4, s));
+    SCHK(hipMemsetAsync(d_info, 0, 4, s));
     hipLaunchKernelGGL(k_lm_blocks, dim3((V.L + 255) / 256), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pose_blocks, dim3((V.n + 15) / 16), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pair_blocks, dim3(V.nblk), dim3(64), 0, s, V);
     if (V.Npad > V.N) hipLaunchKernelGGL(k_pad_identity, dim3((V.Npad - V.N + 63) / 64), dim3(64), 0, s, V);
-    SCHK(hipEventRecord(h->ev[1], s));
+    if (ev_built) SCHK(hipEventRecord(ev_built, s));
     if (h->classic == 1) {  // round 2: one tile column at a time, trailing update with K = 64 (VBA_SCHUR_CLASSIC=2: panels, round-2 tile kernel)
         for (int kb = 0; kb < V.nb; ++kb) {
-            hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(64), 0, s, V, kb, h->d_info);
+            hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(64), 0, s, V, kb, d_info);
             const int rest = V.nb - kb - 1;
             if (rest > 0) {
                 hipLaunchKernelGGL((k_gemm_abt<0>), dim3(rest), dim3(256), 0, s, V, kb, 0);
@@ -894,8 +1080,8 @@ int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, dou
         for (int p = 0; p < np; ++p) {
             const int kb0 = p * kPanel, klast = kb0 + kPanel - 1;
             for (int kb = kb0; kb <= klast; ++kb) {
-                if (h->classic == 2) hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(64), 0, s, V, kb, h->d_info);
-                else hipLaunchKernelGGL(k_potrf64b, dim3(1), dim3(256), 0, s, V, kb, h->d_info);
+                if (h->classic == 2) hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(64), 0, s, V, kb, d_info);
+                else hipLaunchKernelGGL(k_potrf64b, dim3(1), dim3(256), 0, s, V, kb, d_info);
                 const int rest = V.nb - kb - 1;
                 if (rest > 0) hipLaunchKernelGGL((k_gemm_abt<0>), dim3(rest), dim3(256), 0, s, V, kb, 0);
                 if (kb < klast) hipLaunchKernelGGL((k_gemm_abt<2>), dim3(rest, klast - kb), dim3(256), 0, s, V, kb, klast);
@@ -915,6 +1101,21 @@ int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, dou
         }
         if (bulk_pending) SCHK(hipStreamWaitEvent(s, h->ev_bulk, 0));
     }
+    return VBA_OK;
+}
+
+int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, double* cost_after, int* accepted) {
+    if (!h || !cost_before || !cost_after || !accepted) return sfail(VBA_EINVAL, "null argument");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    SCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    SchurView V = h->V;
+    V.lamda = lamda;
+    V.states = h->S0; V.X = h->X0buf; V.states_new = h->S1; V.X_new = h->X1buf;
+    if (int rc = schur_cost(h, V.states, V.X, cost_before)) return rc;
+    SCHK(hipEventRecord(h->ev[0], s));
+    if (int rc = schur_build_factor(h, V, s, h->d_info, h->ev[1])) return rc;
     SCHK(hipEventRecord(h->ev[2], s));
     for (int kb = 0; kb < V.nb; ++kb)
         hipLaunchKernelGGL(k_trsv_step, dim3(1 + std::min(h->bw, V.nb - 1 - kb)), dim3(256), 0, s, V, kb, 0);
@@ -938,6 +1139,129 @@ int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, dou
     if (int rc = schur_cost(h, V.states_new, V.X_new, cost_after)) return rc;
     *accepted = (*cost_after < *cost_before) ? 1 : 0;
     if (*accepted) { std::swap(h->S0, h->S1); std::swap(h->X0buf, h->X1buf); }
+    return VBA_OK;
+}
+
+// first query of a handle: the scratch and its two timing events
+static int schur_query_alloc(vba_schur_handle h) {
+    SchurQuery& Q = h->q;
+    if (Q.arena) return VBA_OK;
+    const SchurView& V = h->V;
+    const size_t m = (size_t)V.m, L = (size_t)V.L, NN = (size_t)V.Npad * V.Npad * 8;
+    size_t bytes = 0;
+    auto need = [&](size_t b) { size_t o = bytes; bytes += (b + 255) & ~size_t(255); return o; };
+    const size_t o_ci = need(L * 48), o_wl = need(L * 24), o_E = need(m * 144), o_Y = need(m * 144), o_S = need(NN), o_g = need((size_t)V.Npad * 8),
+                 o_y = need((size_t)V.Npad * 8), o_iL = need((size_t)V.nb * kT * kT * 8), o_dl = need(L * 24), o_W = need(NN),
+                 o_pair = need((size_t)V.nblk * 288), o_pose = need((size_t)V.n * 288), o_lm = need(L * 72), o_info = need(256),
+                 o_lpp = need((L + 1) * 4), o_lpb = need((size_t)h->npairs * 4);
+    char* A = nullptr;
+    if (hipMalloc(&A, bytes) != hipSuccess) { (void)hipGetLastError(); return sfail(VBA_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes of query scratch failed"); }
+    hipEvent_t ev[2] = {};
+    if (hipMemset(A, 0, bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess || hipEventCreate(&ev[0]) != hipSuccess ||
+        hipEventCreate(&ev[1]) != hipSuccess) {
+        if (ev[0]) hipEventDestroy(ev[0]);
+        hipFree(A);
+        return sfail(VBA_EHIP, "query scratch: hipMemset / event creation failed");
+    }
+    Q.arena = A; Q.ev[0] = ev[0]; Q.ev[1] = ev[1];
+    Q.Cinv = (double*)(A + o_ci); Q.wl = (double*)(A + o_wl); Q.E = (double*)(A + o_E); Q.Y = (double*)(A + o_Y); Q.S = (double*)(A + o_S);
+    Q.g = (double*)(A + o_g); Q.ybuf = (double*)(A + o_y); Q.invL = (double*)(A + o_iL); Q.dl = (double*)(A + o_dl); Q.W = (double*)(A + o_W);
+    Q.pair = (double*)(A + o_pair); Q.pose = (double*)(A + o_pose); Q.lm = (double*)(A + o_lm); Q.info = (int*)(A + o_info);
+    Q.lp_ptr = (int*)(A + o_lpp); Q.lp_blk = (int*)(A + o_lpb);
+    return VBA_OK;
+}
+
+// Once per upload: for every landmark the block of each of its row pairs (k >= k'), in the order k_lm_cov walks them.  The pair
+// lists are grouped by block; they are read back and turned round on the host, and checked on the way (every pair of every
+// landmark exactly once, in the block of its two poses; every diagonal block listed): k_lm_cov and k_cov_gather rely on that.
+static int schur_query_index(vba_schur_handle h) {
+    SchurQuery& Q = h->q;
+    if (Q.indexed) return VBA_OK;
+    const SchurView& V = h->V;
+    const size_t m = (size_t)V.m, np = (size_t)h->npairs;
+    std::vector<int> lm_ptr(V.L + 1), row_pose(m), row_lm(m), bi(V.nblk), bj(V.nblk), bptr(V.nblk + 1), pk(np), pk2(np);
+    auto down = [&](std::vector<int>& dst, const int* src) { return hipMemcpy(dst.data(), src, dst.size() * 4, hipMemcpyDeviceToHost); };
+    SCHK(down(lm_ptr, V.lm_ptr)); SCHK(down(row_pose, V.row_pose)); SCHK(down(row_lm, V.row_lm)); SCHK(down(bi, V.blk_i)); SCHK(down(bj, V.blk_j));
+    SCHK(down(bptr, V.blk_ptr)); SCHK(down(pk, V.pair_k)); SCHK(down(pk2, V.pair_k2));
+    std::vector<int> lp_ptr(V.L + 1, 0);
+    int64_t total = 0;
+    for (int l = 0; l < V.L; ++l) {
+        const int64_t t = lm_ptr[l + 1] - lm_ptr[l];
+        total += t * (t + 1) / 2;
+        if (total > h->npairs) return sfail(VBA_EINVAL, "the pair lists do not hold every row pair of every landmark");
+        lp_ptr[l + 1] = (int)total;
+    }
+    if (total != h->npairs) return sfail(VBA_EINVAL, "the pair lists do not hold every row pair of every landmark");
+    std::vector<int> lp_blk(np, -1);
+    std::vector<char> has_diag(V.n, 0);
+    for (int b = 0; b < V.nblk; ++b) {
+        if (bi[b] == bj[b]) has_diag[bi[b]] = 1;
+        for (int p = bptr[b]; p < bptr[b + 1]; ++p) {
+            const int k = pk[p], k2 = pk2[p], l = row_lm[k];
+            if (row_lm[k2] != l || k2 > k || k2 < lm_ptr[l] || k >= lm_ptr[l + 1] || row_pose[k] != bi[b] || row_pose[k2] != bj[b])
+                return sfail(VBA_EINVAL, "a listed row pair does not belong to its block");
+            const int a = k - lm_ptr[l], c = k2 - lm_ptr[l];
+            int& slot = lp_blk[(size_t)lp_ptr[l] + (size_t)a * (a + 1) / 2 + c];
+            if (slot != -1) return sfail(VBA_EINVAL, "a row pair is listed twice");
+            slot = b;
+        }
+    }
+    // (np pairs into np distinct slots: every slot is filled)
+    for (int i = 0; i < V.n; ++i) if (!has_diag[i]) return sfail(VBA_EINVAL, "the block list lacks a diagonal block");
+    SCHK(hipMemcpy(Q.lp_ptr, lp_ptr.data(), lp_ptr.size() * 4, hipMemcpyHostToDevice));
+    SCHK(hipMemcpy(Q.lp_blk, lp_blk.data(), np * 4, hipMemcpyHostToDevice));
+    Q.indexed = true;
+    return VBA_OK;
+}
+
+int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov, double* pair_cov, double* lm_cov, int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    if (int rc = schur_query_index(h)) return rc;
+    SchurQuery& Q = h->q;
+    hipStream_t s = h->stream;
+    SchurView V = h->V;             // the handle's problem; everything written lives in the scratch
+    V.lamda = lamda;
+    V.states = h->S0; V.X = h->X0buf; V.states_new = nullptr; V.X_new = nullptr; V.part = nullptr;
+    V.Cinv = Q.Cinv; V.wl = Q.wl; V.E = Q.E; V.Y = Q.Y; V.S = Q.S; V.g = Q.g; V.ybuf = Q.ybuf; V.invL = Q.invL; V.dl = Q.dl;
+    SCHK(hipEventRecord(Q.ev[0], s));
+    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr)) return rc;
+    SCHK(hipGetLastError());
+    int bad = 0;
+    SCHK(hipMemcpyAsync(&bad, Q.info, 4, hipMemcpyDeviceToHost, s));
+    SCHK(hipStreamSynchronize(s));
+    *info = bad;
+    const size_t n_pose = (size_t)V.n * 36, n_pair = (size_t)V.nblk * 36, n_lm = (size_t)V.L * 9;
+    if (bad != 0) {                 // no factor, no covariance: NaN, and the row in *info
+        SCHK(hipEventRecord(Q.ev[1], s));
+        SCHK(hipStreamSynchronize(s));
+        (void)hipEventElapsedTime(&Q.ms, Q.ev[0], Q.ev[1]);
+        if (pose_cov) std::fill(pose_cov, pose_cov + n_pose, std::nan(""));
+        if (pair_cov) std::fill(pair_cov, pair_cov + n_pair, std::nan(""));
+        if (lm_cov) std::fill(lm_cov, lm_cov + n_lm, std::nan(""));
+        return VBA_OK;
+    }
+    const int nbu = (V.N + kT - 1) / kT;
+    for (int d = 0; d < nbu; ++d) hipLaunchKernelGGL(k_trinv_step, dim3(nbu - d), dim3(256), 0, s, V, Q.W, d, h->bw);
+    hipLaunchKernelGGL(k_syrk_wtw, dim3(nbu * (nbu + 1) / 2), dim3(256), 0, s, V, Q.W, Q.S, nbu);      // (over the factor: no longer needed)
+    hipLaunchKernelGGL(k_cov_gather, dim3((unsigned)((n_pair + 255) / 256)), dim3(256), 0, s, V, Q.S, Q.pair, Q.pose);
+    if (lm_cov) hipLaunchKernelGGL(k_lm_cov, dim3((V.L + 255) / 256), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm);
+    SCHK(hipEventRecord(Q.ev[1], s));
+    SCHK(hipGetLastError());
+    if (pose_cov) SCHK(hipMemcpyAsync(pose_cov, Q.pose, n_pose * 8, hipMemcpyDeviceToHost, s));
+    if (pair_cov) SCHK(hipMemcpyAsync(pair_cov, Q.pair, n_pair * 8, hipMemcpyDeviceToHost, s));
+    if (lm_cov) SCHK(hipMemcpyAsync(lm_cov, Q.lm, n_lm * 8, hipMemcpyDeviceToHost, s));
+    SCHK(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&Q.ms, Q.ev[0], Q.ev[1]);
+    return VBA_OK;
+}
+
+int vba_schur_last_covariance_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->q.ms;
     return VBA_OK;
 }
 

@@ -152,6 +152,34 @@ class SchurBA:
         self._check(self.lib.vba_schur_debug_fetch(self.h, 1, out.ctypes.data_as(PD), out.size))
         return out
 
+    def covariance(self, lamda=0.0, pairs=False, strict=True):
+        """``vba_schur_covariance`` at the resident state (``include/vinsat_ba.h``): blocks of the inverse of the system an
+        ``iterate(lamda)`` would build there.  Returns a dict: ``pose [n,6,6]`` -- every pose's marginal over all landmarks and
+        all other poses, coordinates ``[dp (km), dtheta]`` -- ``landmark [L,3,3]`` in the caller's landmark order, ``info``,
+        and with ``pairs`` also ``pairs = (blk_i, blk_j, [nblk,6,6])``: the cross-covariances of the poses that share a
+        landmark (``i >= j``, diagonal blocks included).  Up to the variance factor of the weights.  State, step, factor and
+        the bits of the following iterates are not changed.
+
+        A system that is not positive definite at this damping raises ``VbaError`` naming the row (``info - 1``); with
+        ``strict=False`` the arrays come back filled with NaN instead."""
+        pose, lm = np.empty((self.n, 6, 6)), np.empty((self.L, 3, 3))
+        blocks = np.empty((self.structure["blk_i"].size, 6, 6)) if pairs else None
+        info = c_int()
+        self._check(self.lib.vba_schur_covariance(self.h, float(lamda), pose.ctypes.data_as(PD), blocks.ctypes.data_as(PD) if pairs else None,
+                                                  lm.ctypes.data_as(PD), byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur covariance: the reduced camera system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        out = dict(pose=pose, landmark=lm, info=info.value)
+        if pairs:
+            out["pairs"] = (self.structure["blk_i"].copy(), self.structure["blk_j"].copy(), blocks)
+        return out
+
+    def last_covariance_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_covariance_ms(self.h, byref(v)))
+        return v.value
+
     def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10):
         """Levenberg-Marquardt driver: damping x10 on a rejected trial, /10 on an accepted one.  Returns the cost history."""
         lam, hist = float(lamda0), []
@@ -167,3 +195,25 @@ class SchurBA:
                 if lam > 1e8:
                     break
         return hist
+
+
+def tile_bandwidth_of(structure, tile=64):
+    """Largest distance from the diagonal of a non-zero tile of the reduced system, as ``vba_schur_upload`` derives it: the
+    substitutions and the triangular inverse of the covariance query skip the tiles beyond it."""
+    return int(((6 * structure["blk_i"].astype(np.int64) + 5) // tile - (6 * structure["blk_j"].astype(np.int64)) // tile).max())
+
+
+def _blocks(cov, key):
+    return np.asarray(cov[key] if isinstance(cov, dict) else cov, dtype=np.float64)
+
+
+def pose_sigmas(cov):
+    """1-sigma per pose from :meth:`SchurBA.covariance` (its dict, or ``[..., 6, 6]`` blocks): ``(position [..., 3] km,
+    attitude [..., 3] rad)``.  The step's ``dtheta`` linearises a rotation of angle ``2 dtheta``: attitude = ``2 sqrt(.)``."""
+    d = np.diagonal(_blocks(cov, "pose"), axis1=-2, axis2=-1)
+    return np.sqrt(d[..., 0:3]), 2.0 * np.sqrt(d[..., 3:6])
+
+
+def landmark_sigmas(cov):
+    """1-sigma per landmark and axis, km ``[..., 3]``, from :meth:`SchurBA.covariance` (its dict, or ``[..., 3, 3]`` blocks)."""
+    return np.sqrt(np.diagonal(_blocks(cov, "landmark"), axis1=-2, axis2=-1))
