@@ -645,6 +645,36 @@ int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov /*[n
                          double* lm_cov /*[L][3][3] or NULL*/, int* info);
 /* HIP-event time of the last vba_schur_covariance on this handle (build, factorisation, selected inverse and gathers) */
 int vba_schur_last_covariance_ms(vba_schur_handle h, float* ms);
+/* Reliability of the free-landmark fit at the resident state: which observation row, and which catalogue position, the window
+ * contradicts.  H, S, Y_k and the covariance blocks are those of vba_schur_covariance(h, lamda, ...); Sigma = H^-1.  For row k
+ * (landmark-sorted order as uploaded; pose i, landmark l) with A_k = d uv / d [dp, dtheta] (2x6), Al_k = d uv / d X = -A_k[:, :3],
+ * r_k = uv - est and weight w_k:
+ *   Sigma_il    = -sum over the rows k' of l, upwards, of (S^-1)_{i, pose(k')} Y_k'   (6x3 pose-landmark cross-covariance)
+ *   P_k         = w_k [A_k Al_k] [[Sigma_ii, Sigma_il], [Sigma_il^T, Sigma_ll]] [A_k Al_k]^T   (symmetric part)
+ *   leverage[k] = tr P_k,   wtest[k] = sqrt(w_k r_k^T (I - P_k)^-1 r_k)   (2x2 inverse in closed form).
+ *   w_k == 0: leverage 0 and wtest 0; det(I - P_k) <= 0 or a negative quadratic form: wtest NaN (as vba_reliability).
+ * The catalogue prior N(X0, sigma^2 I) of landmark l as an observation, e_l = X_l - X0_l, P_l = Sigma_ll / sigma^2:
+ *   lm_leverage[l] = tr P_l in (0, 3],   lm_wtest[l] = sqrt(e_l^T (I - P_l)^-1 e_l / sigma^2)   (3x3 inverse in closed form; NaN
+ *   for a non-positive determinant or a negative form).  At lamda = 0 a landmark seen from ONE pose has an exactly singular
+ *   I - P_l (its depth is held by the prior alone): its lm_wtest is NaN or a number without meaning -- lm_stats[l][2] tells the
+ *   track length.  A landmark without rows is tested by nothing: lm_wtest 0 and
+ *   lm_leverage = (3.0 * d) * (1.0 / (sigma_prior * sigma_prior)) with the d of vba_schur_covariance, rounded in that order.
+ *   lm_stats[l] = {sum of leverage over the rows of l in row order, largest finite wtest among them (0 if none), number of them
+ *   with w > 0};  pose_stats[i] = the same three over the rows of pose i in the order of pose_rows.
+ *   fit[8] = {Omega = sum w |r|^2 + sum |e_l|^2 / sigma^2 (the cost of vba_schur_iterate, in a summation order of its own),
+ *             m_eff = rows with w > 0, t_rows = sum leverage, t_prior = sum lm_leverage, rho = 2 m_eff + 3 L - t_rows - t_prior,
+ *             s0sq = Omega / rho (NaN if rho <= 0), largest finite row wtest, largest finite landmark wtest}.
+ * Any output may be NULL, in any combination; what is asked for decides the copies only, so the bits do not depend on it.  *info
+ * and the error codes are those of vba_schur_covariance: with *info != 0 every requested output is NaN and the call returns VBA_OK.
+ * The query changes nothing: state, last_info, last_ms, debug_fetch and last_covariance_ms read as before, and the following
+ * iterates and covariance queries return the bits they would have returned without it.  Synchronous.  It uses the covariance
+ * query's scratch and a little of its own, allocated by the first reliability query of a handle.  Every sum has one order (no
+ * float atomics): equal problems give equal bits, across calls and across handles. */
+int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage /*[m] or NULL*/, double* wtest /*[m] or NULL*/,
+                          double* lm_leverage /*[L] or NULL*/, double* lm_wtest /*[L] or NULL*/, double* lm_stats /*[L][3] or NULL*/,
+                          double* pose_stats /*[n][3] or NULL*/, double* fit /*[8] or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_reliability on this handle (the covariance query's device part and the three passes) */
+int vba_schur_last_reliability_ms(vba_schur_handle h, float* ms);
 
 #ifdef __cplusplus
 }

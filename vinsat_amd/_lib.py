@@ -95,6 +95,8 @@ SIGNATURES = {
     "vba_schur_debug_fetch": (c_int, [c_void_p, c_int, PD, c_int64]),
     "vba_schur_covariance": (c_int, [c_void_p, c_double, PD, PD, PD, POINTER(c_int)]),
     "vba_schur_last_covariance_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_reliability": (c_int, [c_void_p, c_double, PD, PD, PD, PD, PD, PD, PD, POINTER(c_int)]),
+    "vba_schur_last_reliability_ms": (c_int, [c_void_p, POINTER(c_float)]),
 }
 
 # VBA_OPT_* of include/vinsat_ba.h (vba_set_option)

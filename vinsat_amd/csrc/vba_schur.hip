@@ -29,6 +29,10 @@
 //   k_syrk_wtw      S^-1 = W^T W on the matrix cores, block per tile of the lower triangle
 //   k_cov_gather    the listed 6x6 blocks of S^-1 (pair_cov) and its diagonal blocks (pose_cov)
 //   k_lm_cov        thread per landmark: C_l^-1 + sum Y_k^T Sigma_{pose(k), pose(k')} Y_k'
+// Reliability query (vba_schur_reliability: the device part of the covariance query, then)
+//   k_rel_rows      thread per row: pose-landmark cross-covariance Sigma_il from the gathered blocks and Y, leverage and w-test
+//   k_rel_stats     thread per landmark / per pose: their rows' statistics; the catalogue prior of a landmark as an observation
+//   k_rel_totals    one block: cost, redundancy, variance factor, largest tests (strided partial sums, one tree)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -40,6 +44,7 @@
 
 #include "../../include/vinsat_ba.h"
 #include "vba_math.h"
+#include "vba_schur_rel_math.h"
 
 namespace {
 
@@ -858,6 +863,178 @@ __global__ __launch_bounds__(256) void k_lm_cov(SchurView V, const double* pair,
     out[6] = o[2]; out[7] = o[4]; out[8] = o[5];
 }
 
+// ------------------------------------------------------------------------------------------------ reliability query
+// vba_schur_reliability, after the device part of the covariance query (gathered blocks, Y, Cinv, landmark marginals resident).
+//
+// Row pass, THREAD PER ROW k (pose i, landmark l, position a in the track of l):
+//   Sigma_il = -sum_{k' in rows(l)} (S^-1)_{i, pose(k')} Y_k'   (6x3, k' upwards; the block of the pair from lp_blk, which lists
+//                                                               k >= k' only: for k' > k the block of (k', k) is read transposed)
+//   P_k = w [A Al] [[Sigma_ii, Sigma_il], [Sigma_il^T, Sigma_ll]] [A Al]^T   (symmetric part), leverage = tr P_k, w-test by
+//   rel_wtest2.  A row costs t products of 6x6 by 6x3 for a track of t rows, so the rows of a landmark together cost the t^2 of
+//   k_lm_cov -- spread over t threads that sit side by side in a wave and read the same Y and the same blocks.
+// om[k] = w |r|^2 is kept for the totals.
+__global__ __launch_bounds__(256) void k_rel_rows(SchurView V, const double* pair, const int* lp_ptr, const int* lp_blk, const double* lm,
+                                                  double* lev, double* wt, double* om) {
+    const int64_t k64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k64 >= V.m) return;
+    const int k = (int)k64;
+    const double w = V.row_w[k];
+    RowGeom q;
+    row_geometry(V, V.states, V.X, k, q);
+    om[k] = w * (q.ru * q.ru + q.rv * q.rv);
+    if (w == 0.0) { lev[k] = 0.0; wt[k] = 0.0; return; }
+    const int l = V.row_lm[k], beg = V.lm_ptr[l], end = V.lm_ptr[l + 1], a = k - beg, base = lp_ptr[l];
+    double G[18];                   // sum (S^-1)_{i, pose(k')} Y_k' = -Sigma_il
+#pragma unroll
+    for (int e = 0; e < 18; ++e) G[e] = 0.0;
+    for (int k2 = beg; k2 < end; ++k2) {
+        const int c = k2 - beg;
+        const bool tr = c > a;
+        const int slot = base + (tr ? c * (c + 1) / 2 + a : a * (a + 1) / 2 + c);
+        const double* Sg = pair + (size_t)lp_blk[slot] * 36;
+        const int sp = tr ? 1 : 6, sq = tr ? 6 : 1;    // entry (p, q) of (S^-1)_{i, pose(k')}: Sg[p sp + q sq]
+        double Y2[18];
+#pragma unroll
+        for (int e = 0; e < 18; ++e) Y2[e] = V.Y[(size_t)k2 * 18 + e];
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+            double g[6];
+#pragma unroll
+            for (int qq = 0; qq < 6; ++qq) g[qq] = Sg[p * sp + qq * sq];
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) {
+                double s = G[3 * p + cc];
+#pragma unroll
+                for (int qq = 0; qq < 6; ++qq) s = fma(g[qq], Y2[3 * qq + cc], s);
+                G[3 * p + cc] = s;
+            }
+        }
+    }
+    double jl[6], jc[12];
+    landmark_jacobian(q, jl);
+    pose_jacobian(q, jl, jc);
+    // A Sigma_ii A^T from the diagonal block of the row's own pair (k, k): stored whole and exactly symmetric
+    const double* Sii = pair + (size_t)lp_blk[base + a * (a + 1) / 2 + a] * 36;
+    double q00 = 0.0, q01 = 0.0, q11 = 0.0;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+        double tu = 0.0, tv = 0.0;
+#pragma unroll
+        for (int qq = 0; qq < 6; ++qq) { tu = fma(Sii[6 * p + qq], jc[qq], tu); tv = fma(Sii[6 * p + qq], jc[6 + qq], tv); }
+        q00 = fma(jc[p], tu, q00);
+        q01 = fma(jc[p], tv, q01);
+        q11 = fma(jc[6 + p], tv, q11);
+    }
+    // A (-Sigma_il) Al^T: x = A G (2x3), then against the rows of Al
+    double x00 = 0.0, x01 = 0.0, x10 = 0.0, x11 = 0.0;
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) {
+        double xu = 0.0, xv = 0.0;
+#pragma unroll
+        for (int p = 0; p < 6; ++p) { xu = fma(jc[p], G[3 * p + cc], xu); xv = fma(jc[6 + p], G[3 * p + cc], xv); }
+        x00 = fma(xu, jl[cc], x00);
+        x01 = fma(xu, jl[3 + cc], x01);
+        x10 = fma(xv, jl[cc], x10);
+        x11 = fma(xv, jl[3 + cc], x11);
+    }
+    // Al Sigma_ll Al^T
+    const double* Sl = lm + (size_t)l * 9;
+    double l00 = 0.0, l01 = 0.0, l11 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double yu = fma(Sl[3 * r], jl[0], fma(Sl[3 * r + 1], jl[1], Sl[3 * r + 2] * jl[2]));
+        const double yv = fma(Sl[3 * r], jl[3], fma(Sl[3 * r + 1], jl[4], Sl[3 * r + 2] * jl[5]));
+        l00 = fma(jl[r], yu, l00);
+        l01 = fma(jl[r], yv, l01);
+        l11 = fma(jl[3 + r], yv, l11);
+    }
+    const double p00 = w * ((q00 + l00) - (x00 + x00));
+    const double p01 = w * ((q01 + l01) - (x01 + x10));
+    const double p11 = w * ((q11 + l11) - (x11 + x11));
+    lev[k] = p00 + p11;
+    wt[k] = rel_wtest2(p00, p01, p11, q.ru, q.rv, w);
+}
+
+// sum of leverage, largest finite w-test, count of rows with w > 0 over a list of rows in list order (idx == nullptr: beg .. end)
+__device__ __forceinline__ void rel_row_stats(const SchurView& V, const int* idx, int beg, int end, const double* lev, const double* wt, double* out) {
+    double s = 0.0, mx = 0.0, cnt = 0.0;
+    for (int r = beg; r < end; ++r) {
+        const int k = idx ? idx[r] : r;
+        s += lev[k];
+        const double t = wt[k];
+        if (t <= 1.79e308 && t > mx) mx = t;    // (NaN fails both)
+        cnt += V.row_w[k] > 0.0 ? 1.0 : 0.0;
+    }
+    out[0] = s; out[1] = mx; out[2] = cnt;
+}
+
+// Thread id < L: the statistics of landmark id over its rows and the test of its catalogue prior as an observation,
+// e = X - X0, P_l = Sigma_ll / sigma^2; lmom = |e|^2 / sigma^2 is kept for the totals.  Thread id < n: the statistics of pose id.
+__global__ __launch_bounds__(256) void k_rel_stats(SchurView V, const double* lm, const double* lev, const double* wt, double* lmlev, double* lmwt,
+                                                   double* lmom, double* lm_stats, double* pose_stats) {
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id < V.L) {
+        const int l = id, beg = V.lm_ptr[l], end = V.lm_ptr[l + 1];
+        rel_row_stats(V, nullptr, beg, end, lev, wt, lm_stats + (size_t)l * 3);
+        const double e[3] = {V.X[3 * l] - V.X0[3 * l], V.X[3 * l + 1] - V.X0[3 * l + 1], V.X[3 * l + 2] - V.X0[3 * l + 2]};
+        lmom[l] = V.inv_sigma2 * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+        if (beg == end) {           // tested by nothing: the closed form of k_lm_cov's d
+            const double d = 1.0 / (V.inv_sigma2 + V.lamda);
+            lmlev[l] = (3.0 * d) * V.inv_sigma2;
+            lmwt[l] = 0.0;
+        } else {
+            const double* Sl = lm + (size_t)l * 9;
+            const double is2 = V.inv_sigma2;
+            const double p[6] = {Sl[0] * is2, Sl[1] * is2, Sl[2] * is2, Sl[4] * is2, Sl[5] * is2, Sl[8] * is2};
+            lmlev[l] = (p[0] + p[3]) + p[5];
+            const double mI[6] = {1.0 - p[0], -p[1], -p[2], 1.0 - p[3], -p[4], 1.0 - p[5]};
+            lmwt[l] = rel_wtest3(mI, e, is2);
+        }
+    }
+    if (id < V.n) rel_row_stats(V, V.pose_rows, V.pose_ptr[id], V.pose_ptr[id + 1], lev, wt, pose_stats + (size_t)id * 3);
+}
+
+// Totals, ONE block: thread t sums the rows t, t + 256, ... and the landmarks likewise, then a tree over the 256 partials -- one
+// shape for every problem.  fit[8] = Omega, m_eff, t_rows, t_prior, rho, s0sq, largest finite row / landmark w-test.
+__global__ __launch_bounds__(256) void k_rel_totals(SchurView V, const double* lev, const double* wt, const double* om, const double* lmlev,
+                                                    const double* lmwt, const double* lmom, double* fit) {
+    __shared__ double red[7][256];
+    const int t = threadIdx.x;
+    double a[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // om rows, m_eff, t_rows, max row, om prior, t_prior, max landmark
+    for (int64_t k = t; k < V.m; k += 256) {
+        a[0] += om[k];
+        a[1] += V.row_w[k] > 0.0 ? 1.0 : 0.0;
+        a[2] += lev[k];
+        const double x = wt[k];
+        if (x <= 1.79e308 && x > a[3]) a[3] = x;
+    }
+    for (int l = t; l < V.L; l += 256) {
+        a[4] += lmom[l];
+        a[5] += lmlev[l];
+        const double x = lmwt[l];
+        if (x <= 1.79e308 && x > a[6]) a[6] = x;
+    }
+#pragma unroll
+    for (int e = 0; e < 7; ++e) red[e][t] = a[e];
+    for (int o = 128; o > 0; o >>= 1) {
+        __syncthreads();
+        if (t < o) {
+#pragma unroll
+            for (int e = 0; e < 7; ++e) {
+                const double x = red[e][t], y = red[e][t + o];
+                red[e][t] = (e == 3 || e == 6) ? (y > x ? y : x) : x + y;
+            }
+        }
+    }
+    if (t == 0) {
+        const double Omega = red[0][0] + red[4][0], meff = red[1][0], trows = red[2][0], tprior = red[5][0];
+        const double rho = ((2.0 * meff + 3.0 * (double)V.L) - trows) - tprior;
+        fit[0] = Omega; fit[1] = meff; fit[2] = trows; fit[3] = tprior; fit[4] = rho;
+        fit[5] = rho > 0.0 ? Omega / rho : __builtin_nan("");
+        fit[6] = red[3][0]; fit[7] = red[6][0];
+    }
+}
+
 // Scratch of vba_schur_covariance, allocated by the first query of a handle: every array the build and the factorisation write,
 // W, the gathered blocks and the landmarks' pair -> block index (built on the host from the uploaded lists, once per upload).
 struct SchurQuery {
@@ -867,6 +1044,16 @@ struct SchurQuery {
     int *info = nullptr, *lp_ptr = nullptr, *lp_blk = nullptr;
     hipEvent_t ev[2] = {};
     bool indexed = false;
+    float ms = 0.0f;
+};
+
+// What vba_schur_reliability needs beyond that, allocated by the first reliability query of a handle: its outputs on the device,
+// the per-row and per-landmark cost terms of the totals, and two timing events of its own.
+struct SchurRel {
+    char* arena = nullptr;
+    double *lev = nullptr, *wt = nullptr, *om = nullptr, *lmlev = nullptr, *lmwt = nullptr, *lmom = nullptr, *lm_stats = nullptr,
+           *pose_stats = nullptr, *fit = nullptr;
+    hipEvent_t ev[2] = {};
     float ms = 0.0f;
 };
 
@@ -900,6 +1087,7 @@ struct vba_schur_context {
     float ms[4] = {0, 0, 0, 0};
     int64_t npairs = 0;
     SchurQuery q;               // vba_schur_covariance's scratch (nothing until the first query)
+    SchurRel rel;               // vba_schur_reliability's scratch on top of it (nothing until the first reliability query)
     int bw = 1 << 30;           // tile bandwidth of the reduced system (max |I - J| over its non-zero tiles), from the block list
 };
 
@@ -969,6 +1157,8 @@ int vba_schur_destroy(vba_schur_handle h) {
     if (h->ev_bulk) hipEventDestroy(h->ev_bulk);
     for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : h->q.ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : h->rel.ev) if (e) hipEventDestroy(e);
+    if (h->rel.arena) hipFree(h->rel.arena);
     if (h->q.arena) hipFree(h->q.arena);
     if (h->arena) hipFree(h->arena);
     delete h;
@@ -1214,6 +1404,33 @@ static int schur_query_index(vba_schur_handle h) {
     return VBA_OK;
 }
 
+// The device part of vba_schur_covariance, shared with vba_schur_reliability: ev_begin, then build and factorise into the query's
+// scratch at this damping (V: the view that was built -- the handle's problem, everything written in the scratch), the info word
+// to the host (*bad), and unless the factorisation failed the selected inverse, the gathered blocks (Q.pair, Q.pose) and, with
+// with_lm, the landmark marginals (Q.lm).  The launches and their order are those vba_schur_covariance has always issued.
+static int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad) {
+    SchurQuery& Q = h->q;
+    hipStream_t s = h->stream;
+    V = h->V;
+    V.lamda = lamda;
+    V.states = h->S0; V.X = h->X0buf; V.states_new = nullptr; V.X_new = nullptr; V.part = nullptr;
+    V.Cinv = Q.Cinv; V.wl = Q.wl; V.E = Q.E; V.Y = Q.Y; V.S = Q.S; V.g = Q.g; V.ybuf = Q.ybuf; V.invL = Q.invL; V.dl = Q.dl;
+    SCHK(hipEventRecord(ev_begin, s));
+    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr)) return rc;
+    SCHK(hipGetLastError());
+    *bad = 0;
+    SCHK(hipMemcpyAsync(bad, Q.info, 4, hipMemcpyDeviceToHost, s));
+    SCHK(hipStreamSynchronize(s));
+    if (*bad != 0) return VBA_OK;
+    const int nbu = (V.N + kT - 1) / kT;
+    const size_t n_pair = (size_t)V.nblk * 36;
+    for (int d = 0; d < nbu; ++d) hipLaunchKernelGGL(k_trinv_step, dim3(nbu - d), dim3(256), 0, s, V, Q.W, d, h->bw);
+    hipLaunchKernelGGL(k_syrk_wtw, dim3(nbu * (nbu + 1) / 2), dim3(256), 0, s, V, Q.W, Q.S, nbu);      // (over the factor: no longer needed)
+    hipLaunchKernelGGL(k_cov_gather, dim3((unsigned)((n_pair + 255) / 256)), dim3(256), 0, s, V, Q.S, Q.pair, Q.pose);
+    if (with_lm) hipLaunchKernelGGL(k_lm_cov, dim3((V.L + 255) / 256), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm);
+    return VBA_OK;
+}
+
 int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov, double* pair_cov, double* lm_cov, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
@@ -1223,16 +1440,9 @@ int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov, dou
     if (int rc = schur_query_index(h)) return rc;
     SchurQuery& Q = h->q;
     hipStream_t s = h->stream;
-    SchurView V = h->V;             // the handle's problem; everything written lives in the scratch
-    V.lamda = lamda;
-    V.states = h->S0; V.X = h->X0buf; V.states_new = nullptr; V.X_new = nullptr; V.part = nullptr;
-    V.Cinv = Q.Cinv; V.wl = Q.wl; V.E = Q.E; V.Y = Q.Y; V.S = Q.S; V.g = Q.g; V.ybuf = Q.ybuf; V.invL = Q.invL; V.dl = Q.dl;
-    SCHK(hipEventRecord(Q.ev[0], s));
-    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr)) return rc;
-    SCHK(hipGetLastError());
+    SchurView V;
     int bad = 0;
-    SCHK(hipMemcpyAsync(&bad, Q.info, 4, hipMemcpyDeviceToHost, s));
-    SCHK(hipStreamSynchronize(s));
+    if (int rc = schur_query_device(h, lamda, lm_cov != nullptr, Q.ev[0], V, &bad)) return rc;
     *info = bad;
     const size_t n_pose = (size_t)V.n * 36, n_pair = (size_t)V.nblk * 36, n_lm = (size_t)V.L * 9;
     if (bad != 0) {                 // no factor, no covariance: NaN, and the row in *info
@@ -1244,11 +1454,6 @@ int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov, dou
         if (lm_cov) std::fill(lm_cov, lm_cov + n_lm, std::nan(""));
         return VBA_OK;
     }
-    const int nbu = (V.N + kT - 1) / kT;
-    for (int d = 0; d < nbu; ++d) hipLaunchKernelGGL(k_trinv_step, dim3(nbu - d), dim3(256), 0, s, V, Q.W, d, h->bw);
-    hipLaunchKernelGGL(k_syrk_wtw, dim3(nbu * (nbu + 1) / 2), dim3(256), 0, s, V, Q.W, Q.S, nbu);      // (over the factor: no longer needed)
-    hipLaunchKernelGGL(k_cov_gather, dim3((unsigned)((n_pair + 255) / 256)), dim3(256), 0, s, V, Q.S, Q.pair, Q.pose);
-    if (lm_cov) hipLaunchKernelGGL(k_lm_cov, dim3((V.L + 255) / 256), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm);
     SCHK(hipEventRecord(Q.ev[1], s));
     SCHK(hipGetLastError());
     if (pose_cov) SCHK(hipMemcpyAsync(pose_cov, Q.pose, n_pose * 8, hipMemcpyDeviceToHost, s));
@@ -1262,6 +1467,77 @@ int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov, dou
 int vba_schur_last_covariance_ms(vba_schur_handle h, float* ms) {
     if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
     *ms = h->q.ms;
+    return VBA_OK;
+}
+
+// first reliability query of a handle: its scratch and its two timing events
+static int schur_rel_alloc(vba_schur_handle h) {
+    SchurRel& R = h->rel;
+    if (R.arena) return VBA_OK;
+    const SchurView& V = h->V;
+    const size_t m = (size_t)V.m, L = (size_t)V.L;
+    size_t bytes = 0;
+    auto need = [&](size_t b) { size_t o = bytes; bytes += (b + 255) & ~size_t(255); return o; };
+    const size_t o_lev = need(m * 8), o_wt = need(m * 8), o_om = need(m * 8), o_ll = need(L * 8), o_lw = need(L * 8), o_lo = need(L * 8),
+                 o_ls = need(L * 24), o_ps = need((size_t)V.n * 24), o_fit = need(64);
+    char* A = nullptr;
+    if (hipMalloc(&A, bytes) != hipSuccess) { (void)hipGetLastError(); return sfail(VBA_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes of reliability scratch failed"); }
+    hipEvent_t ev[2] = {};
+    if (hipMemset(A, 0, bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess || hipEventCreate(&ev[0]) != hipSuccess ||
+        hipEventCreate(&ev[1]) != hipSuccess) {
+        if (ev[0]) hipEventDestroy(ev[0]);
+        hipFree(A);
+        return sfail(VBA_EHIP, "reliability scratch: hipMemset / event creation failed");
+    }
+    R.arena = A; R.ev[0] = ev[0]; R.ev[1] = ev[1];
+    R.lev = (double*)(A + o_lev); R.wt = (double*)(A + o_wt); R.om = (double*)(A + o_om); R.lmlev = (double*)(A + o_ll); R.lmwt = (double*)(A + o_lw);
+    R.lmom = (double*)(A + o_lo); R.lm_stats = (double*)(A + o_ls); R.pose_stats = (double*)(A + o_ps); R.fit = (double*)(A + o_fit);
+    return VBA_OK;
+}
+
+int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
+                          double* lm_stats, double* pose_stats, double* fit, int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    if (int rc = schur_query_index(h)) return rc;
+    if (int rc = schur_rel_alloc(h)) return rc;
+    SchurQuery& Q = h->q;
+    SchurRel& R = h->rel;
+    hipStream_t s = h->stream;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_query_device(h, lamda, true, R.ev[0], V, &bad)) return rc;
+    *info = bad;
+    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
+    struct Out { double* host; const double* dev; size_t count; };
+    const Out outs[7] = {{leverage, R.lev, m}, {wtest, R.wt, m}, {lm_leverage, R.lmlev, L}, {lm_wtest, R.lmwt, L}, {lm_stats, R.lm_stats, 3 * L},
+                         {pose_stats, R.pose_stats, 3 * n}, {fit, R.fit, 8}};
+    if (bad != 0) {                 // no factor, no covariance, no test: NaN, and the row in *info
+        SCHK(hipEventRecord(R.ev[1], s));
+        SCHK(hipStreamSynchronize(s));
+        (void)hipEventElapsedTime(&R.ms, R.ev[0], R.ev[1]);
+        for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
+        return VBA_OK;
+    }
+    // every output is formed whatever is asked for: what is asked for decides the copies only
+    hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
+    hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
+                       R.pose_stats);
+    hipLaunchKernelGGL(k_rel_totals, dim3(1), dim3(256), 0, s, V, R.lev, R.wt, R.om, R.lmlev, R.lmwt, R.lmom, R.fit);
+    SCHK(hipEventRecord(R.ev[1], s));
+    SCHK(hipGetLastError());
+    for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
+    SCHK(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&R.ms, R.ev[0], R.ev[1]);
+    return VBA_OK;
+}
+
+int vba_schur_last_reliability_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->rel.ms;
     return VBA_OK;
 }
 

@@ -21,6 +21,10 @@ from . import _lib
 from ._lib import PD
 
 
+# fit[8] of vba_schur_reliability, in its order
+FIT_NAMES = ("omega", "m_eff", "t_rows", "t_prior", "rho", "s0sq", "max_wtest", "max_lm_wtest")
+
+
 def build_structure(pose_of_row, landmark_of_row, n, L):
     """Static index structure of a window (see ``include/vinsat_ba.h``, ``vba_schur_upload``).
 
@@ -180,6 +184,36 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_covariance_ms(self.h, byref(v)))
         return v.value
 
+    def reliability(self, lamda=0.0, strict=True):
+        """``vba_schur_reliability`` at the resident state (``include/vinsat_ba.h``): which row, and which catalogue position,
+        the window contradicts.  Returns a dict: ``leverage [m]`` (trace of the row's 2x2 block of the hat matrix, poses AND
+        landmark free) and ``wtest [m]`` in the CALLER's row order; ``lm_leverage [L]`` / ``lm_wtest [L]``, the same for the
+        catalogue prior of every landmark taken as an observation; ``lm_stats [L,3]`` and ``pose_stats [n,3]`` = (sum of
+        leverage, largest finite wtest, rows with ``w > 0``) per landmark / pose; ``fit``, a dict of :data:`FIT_NAMES`; ``info``.
+        Up to the variance factor of the weights (``fit["s0sq"]`` estimates it).  Nothing on the handle changes.
+
+        ``strict`` as in :meth:`covariance`: a system that is not positive definite raises, or gives NaN everywhere."""
+        out = dict(leverage=np.empty(self.m), wtest=np.empty(self.m), lm_leverage=np.empty(self.L), lm_wtest=np.empty(self.L),
+                   lm_stats=np.empty((self.L, 3)), pose_stats=np.empty((self.n, 3)))
+        fit, info = np.empty(len(FIT_NAMES)), c_int()
+        self._check(self.lib.vba_schur_reliability(self.h, float(lamda), *[a.ctypes.data_as(PD) for a in out.values()], fit.ctypes.data_as(PD),
+                                                   byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur reliability: the reduced camera system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        for key in ("leverage", "wtest"):               # device rows are sorted by landmark: back to the caller's order
+            back = np.empty(self.m)
+            back[self.order] = out[key]
+            out[key] = back
+        out["fit"] = dict(zip(FIT_NAMES, fit.tolist()))
+        out["info"] = info.value
+        return out
+
+    def last_reliability_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_reliability_ms(self.h, byref(v)))
+        return v.value
+
     def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10):
         """Levenberg-Marquardt driver: damping x10 on a rejected trial, /10 on an accepted one.  Returns the cost history."""
         lam, hist = float(lamda0), []
@@ -195,6 +229,15 @@ class SchurBA:
                 if lam > 1e8:
                     break
         return hist
+
+
+def suspects(rel, crit, scaled=False):
+    """``(rows, landmarks)``: the indices (caller's order, ascending) of the rows whose ``wtest`` and of the landmarks whose
+    ``lm_wtest`` exceed ``crit`` in the dict of :meth:`SchurBA.reliability` -- ``crit * sqrt(s0sq)`` with ``scaled`` (weights
+    known up to their variance factor).  NaN tests exceed nothing."""
+    thr = float(crit) * (np.sqrt(rel["fit"]["s0sq"]) if scaled else 1.0)
+    with np.errstate(invalid="ignore"):
+        return np.nonzero(rel["wtest"] > thr)[0], np.nonzero(rel["lm_wtest"] > thr)[0]
 
 
 def tile_bandwidth_of(structure, tile=64):
