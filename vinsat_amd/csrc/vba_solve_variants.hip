@@ -226,7 +226,9 @@ __global__ __launch_bounds__(64) void k_solve_packed(DevView V) {
         WinScalars& s3 = V.sc[w];
         if (s3.done || !VBA_WINDOW_RUNS(V, w) || !solver_mine<PIVOT>(V, s3)) continue;
         const unsigned long long gm = ((1ull << 19) - 1ull) << (19 * q3);
-        if (lane == 0 && (badmask & gm)) atomicOr(&s3.fl[V.par], PIVOT ? 4u : 8u);
+        // (as report_pivot: 8 asks the host for the pivoted repeat, 16 hands the window to the pivoted kernels -- without it
+        // solver_mine<true> turned the window away and the repeat never reported an outcome)
+        if (lane == 0 && (badmask & gm)) atomicOr(&s3.fl[V.par], PIVOT ? 4u : (8u | 16u));
         const bool bad = retract_range(V, (size_t)w * V.n_max, n, lane, 64);
         const unsigned long long anybad = __ballot(bad);
         if (lane == 0 && anybad) atomicOr(&s3.fl[V.par], 2u);
