@@ -675,6 +675,41 @@ int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage /*[
                           double* pose_stats /*[n][3] or NULL*/, double* fit /*[8] or NULL*/, int* info);
 /* HIP-event time of the last vba_schur_reliability on this handle (the covariance query's device part and the three passes) */
 int vba_schur_last_reliability_ms(vba_schur_handle h, float* ms);
+/* Data snooping of the free-landmark fit: one call runs the device part of vba_schur_reliability(h, lamda, ...) at the resident
+ * state, picks what to reject by the fixed rule below and zeroes the weights of the rejected rows in place, on the device.
+ * Rejecting a ROW: its weight in the handle's weight array becomes 0.0; the value it had is kept.  Rejecting a CATALOGUE ENTRY:
+ * the landmark leaves the window -- every row of it with w > 0 gets weight 0 (values kept likewise) and its byte in the landmark
+ * mask is set; its prior then holds it at X0 and it no longer pulls any pose.  At most one rejection per group and call.
+ *   c = crit, or crit * sqrt(s0sq) with scaled != 0, s0sq = fit[5] read on the device (the correctly rounded root, one product);
+ *   returned in *crit_used.  A non-finite c rejects nothing; so does a call with *info != 0 (then *crit_used is NaN if scaled).
+ *   cntl_l / cnt_i = rows of landmark l / pose i with w > 0.  Row candidate: w_k > 0, wtest[k] finite and > c.  Prior candidate:
+ *   cntl_l >= min_track, lm_wtest[l] finite and > c.
+ *   1. Per landmark: among its row candidates and its prior candidate the largest test wins; among rows ties go to the smaller
+ *      sorted row; a row beats the prior on a tie; a NaN never wins.  The prior wins: the landmark is MARKED.  A row wins: the
+ *      landmark PROPOSES that row.
+ *   2. Per pose, in pose_rows order: c_lm_i = its weighted rows on marked landmarks; the pose is SHORT if cnt_i - c_lm_i <
+ *      min_rows; its best proposed row (largest wtest, ties to the smaller sorted row) is rejected iff the pose is not short and
+ *      cnt_i - c_lm_i - 1 >= min_rows.
+ *   3. Per landmark: a marked landmark is rejected iff none of the poses of its weighted rows is short; otherwise nothing happens
+ *      to it in this call (no cascade).
+ * counts[3] = {rows rejected by their own test, landmarks rejected, rows zeroed through rejected landmarks} of this call;
+ * counts and crit_used may be NULL.  *info as vba_schur_reliability.  From the call's return the handle gives, bit for bit, what a
+ * fresh handle gives that was uploaded with the same structure, those rows' weights zeroed, and the same state set
+ * (vba_schur_iterate, vba_schur_covariance, vba_schur_reliability).  A call that rejects nothing changes nothing: state,
+ * last_info, last_ms, debug_fetch, last_covariance_ms and last_reliability_ms read as before.  The feature's state (a double and
+ * a byte per row, a byte per landmark, a few ints per pose and landmark) is allocated by the first snoop of a handle and lives
+ * until vba_schur_upload, which clears it.  Synchronous; no atomics: equal problems give equal masks.
+ * Errors: as vba_schur_reliability; VBA_EINVAL also for a NaN or negative crit and for a negative min_rows or min_track. */
+int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts /*[3] or NULL*/,
+                    double* crit_used /*or NULL*/, int* info);
+/* Cumulative since the last upload or restore: row_mask [m] in the sorted row order of the upload, lm_mask [L], totals[3] as the
+ * counts of vba_schur_snoop.  Any output may be NULL.  All zero on a handle that never snooped. */
+int vba_schur_rejected(vba_schur_handle h, unsigned char* row_mask /*[m] or NULL*/, unsigned char* lm_mask /*[L] or NULL*/, int* totals /*[3] or NULL*/);
+/* The saved weights back in place, both masks and the totals cleared: the handle gives the bits of one that never snooped.  A
+ * no-op on a handle that never snooped. */
+int vba_schur_snoop_restore(vba_schur_handle h);
+/* HIP-event time of the last vba_schur_snoop on this handle (the reliability query's device part and the passes of the rule) */
+int vba_schur_last_snoop_ms(vba_schur_handle h, float* ms);
 
 #ifdef __cplusplus
 }

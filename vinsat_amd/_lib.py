@@ -97,6 +97,10 @@ SIGNATURES = {
     "vba_schur_last_covariance_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_reliability": (c_int, [c_void_p, c_double, PD, PD, PD, PD, PD, PD, PD, POINTER(c_int)]),
     "vba_schur_last_reliability_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_snoop": (c_int, [c_void_p, c_double, c_double, c_int, c_int, c_int, POINTER(c_int), PD, POINTER(c_int)]),
+    "vba_schur_rejected": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
+    "vba_schur_snoop_restore": (c_int, [c_void_p]),
+    "vba_schur_last_snoop_ms": (c_int, [c_void_p, POINTER(c_float)]),
 }
 
 # VBA_OPT_* of include/vinsat_ba.h (vba_set_option)

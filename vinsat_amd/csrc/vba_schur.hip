@@ -33,6 +33,7 @@
 //   k_rel_rows      thread per row: pose-landmark cross-covariance Sigma_il from the gathered blocks and Y, leverage and w-test
 //   k_rel_stats     thread per landmark / per pose: their rows' statistics; the catalogue prior of a landmark as an observation
 //   k_rel_totals    one block: cost, redundancy, variance factor, largest tests (strided partial sums, one tree)
+// Data snooping (vba_schur_snoop: the device part of the reliability query, then the passes of vba_schur_snoop.hip)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -45,6 +46,7 @@
 #include "../../include/vinsat_ba.h"
 #include "vba_math.h"
 #include "vba_schur_rel_math.h"
+#include "vba_schur_snoop.h"
 
 namespace {
 
@@ -1057,6 +1059,18 @@ struct SchurRel {
     float ms = 0.0f;
 };
 
+// State of vba_schur_snoop, allocated by the first snoop of a handle and cleared by vba_schur_upload: the weight a rejected row
+// had and a byte per row, a byte per landmark (both cumulative), the per-call decisions of the passes, two timing events.
+struct SchurSnoop {
+    char* arena = nullptr;
+    double *saved = nullptr, *crit_used = nullptr;
+    unsigned char *row_mask = nullptr, *lm_mask = nullptr;
+    int *lm_dec = nullptr, *pose_pick = nullptr, *pose_short = nullptr, *pose_out = nullptr, *lm_out = nullptr;
+    hipEvent_t ev[2] = {};
+    int totals[3] = {0, 0, 0};  // rows rejected by their own test, landmarks rejected, rows zeroed through rejected landmarks
+    float ms = 0.0f;
+};
+
 thread_local std::string g_serr;
 int sfail(int code, const std::string& msg) { g_serr = msg; return code; }
 
@@ -1088,6 +1102,7 @@ struct vba_schur_context {
     int64_t npairs = 0;
     SchurQuery q;               // vba_schur_covariance's scratch (nothing until the first query)
     SchurRel rel;               // vba_schur_reliability's scratch on top of it (nothing until the first reliability query)
+    SchurSnoop snoop;           // vba_schur_snoop's state (nothing until the first snoop)
     int bw = 1 << 30;           // tile bandwidth of the reduced system (max |I - J| over its non-zero tiles), from the block list
 };
 
@@ -1158,6 +1173,8 @@ int vba_schur_destroy(vba_schur_handle h) {
     for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : h->q.ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : h->rel.ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : h->snoop.ev) if (e) hipEventDestroy(e);
+    if (h->snoop.arena) hipFree(h->snoop.arena);
     if (h->rel.arena) hipFree(h->rel.arena);
     if (h->q.arena) hipFree(h->q.arena);
     if (h->arena) hipFree(h->arena);
@@ -1202,6 +1219,12 @@ int vba_schur_upload(vba_schur_handle h, const int* lm_ptr, const int* row_pose,
     h->bw = 0;
     for (int b = 0; b < V.nblk; ++b) h->bw = std::max(h->bw, (6 * blk_i[b] + 5) / kT - (6 * blk_j[b]) / kT);
     h->q.indexed = false;
+    if (h->snoop.arena) {       // new weights: nothing is rejected
+        SCHK(hipMemset(h->snoop.row_mask, 0, (size_t)V.m));
+        SCHK(hipMemset(h->snoop.lm_mask, 0, (size_t)V.L));
+        SCHK(hipStreamSynchronize(nullptr));
+        std::fill(h->snoop.totals, h->snoop.totals + 3, 0);
+    }
     h->uploaded = true;
     return VBA_OK;
 }
@@ -1495,6 +1518,23 @@ static int schur_rel_alloc(vba_schur_handle h) {
     return VBA_OK;
 }
 
+// The device part of vba_schur_reliability, shared with vba_schur_snoop: schur_query_device with the landmark marginals from
+// ev_begin on, and unless the factorisation failed (*bad != 0: nothing more is launched) the three passes into the reliability
+// scratch.  The launches and their order are those vba_schur_reliability has always issued.
+static int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad) {
+    SchurQuery& Q = h->q;
+    SchurRel& R = h->rel;
+    hipStream_t s = h->stream;
+    if (int rc = schur_query_device(h, lamda, true, ev_begin, V, bad)) return rc;
+    if (*bad != 0) return VBA_OK;
+    // every output is formed whatever is asked for: what is asked for decides the copies only
+    hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
+    hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
+                       R.pose_stats);
+    hipLaunchKernelGGL(k_rel_totals, dim3(1), dim3(256), 0, s, V, R.lev, R.wt, R.om, R.lmlev, R.lmwt, R.lmom, R.fit);
+    return VBA_OK;
+}
+
 int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
                           double* lm_stats, double* pose_stats, double* fit, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
@@ -1504,12 +1544,11 @@ int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, do
     if (int rc = schur_query_alloc(h)) return rc;
     if (int rc = schur_query_index(h)) return rc;
     if (int rc = schur_rel_alloc(h)) return rc;
-    SchurQuery& Q = h->q;
     SchurRel& R = h->rel;
     hipStream_t s = h->stream;
     SchurView V;
     int bad = 0;
-    if (int rc = schur_query_device(h, lamda, true, R.ev[0], V, &bad)) return rc;
+    if (int rc = schur_rel_device(h, lamda, R.ev[0], V, &bad)) return rc;
     *info = bad;
     const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
     struct Out { double* host; const double* dev; size_t count; };
@@ -1522,11 +1561,6 @@ int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, do
         for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
         return VBA_OK;
     }
-    // every output is formed whatever is asked for: what is asked for decides the copies only
-    hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
-    hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
-                       R.pose_stats);
-    hipLaunchKernelGGL(k_rel_totals, dim3(1), dim3(256), 0, s, V, R.lev, R.wt, R.om, R.lmlev, R.lmwt, R.lmom, R.fit);
     SCHK(hipEventRecord(R.ev[1], s));
     SCHK(hipGetLastError());
     for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
@@ -1538,6 +1572,136 @@ int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, do
 int vba_schur_last_reliability_ms(vba_schur_handle h, float* ms) {
     if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
     *ms = h->rel.ms;
+    return VBA_OK;
+}
+
+// first snoop of a handle: its state (masks cleared) and its two timing events
+static int schur_snoop_alloc(vba_schur_handle h) {
+    SchurSnoop& Z = h->snoop;
+    if (Z.arena) return VBA_OK;
+    const SchurView& V = h->V;
+    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
+    size_t bytes = 0;
+    auto need = [&](size_t b) { size_t o = bytes; bytes += (b + 255) & ~size_t(255); return o; };
+    const size_t o_sv = need(m * 8), o_cr = need(8), o_rm = need(m), o_lk = need(L), o_ld = need(L * 4), o_pp = need(n * 4), o_ps = need(n * 4),
+                 o_po = need(n * 4), o_lo = need(L * 4);
+    char* A = nullptr;
+    if (hipMalloc(&A, bytes) != hipSuccess) { (void)hipGetLastError(); return sfail(VBA_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes of snooping state failed"); }
+    hipEvent_t ev[2] = {};
+    if (hipMemset(A, 0, bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess || hipEventCreate(&ev[0]) != hipSuccess ||
+        hipEventCreate(&ev[1]) != hipSuccess) {
+        if (ev[0]) hipEventDestroy(ev[0]);
+        hipFree(A);
+        return sfail(VBA_EHIP, "snooping state: hipMemset / event creation failed");
+    }
+    Z.arena = A; Z.ev[0] = ev[0]; Z.ev[1] = ev[1];
+    Z.saved = (double*)(A + o_sv); Z.crit_used = (double*)(A + o_cr); Z.row_mask = (unsigned char*)(A + o_rm); Z.lm_mask = (unsigned char*)(A + o_lk);
+    Z.lm_dec = (int*)(A + o_ld); Z.pose_pick = (int*)(A + o_pp); Z.pose_short = (int*)(A + o_ps); Z.pose_out = (int*)(A + o_po); Z.lm_out = (int*)(A + o_lo);
+    std::fill(Z.totals, Z.totals + 3, 0);
+    return VBA_OK;
+}
+
+static SchurSnoopView schur_snoop_view(vba_schur_handle h) {
+    const SchurView& V = h->V;
+    const SchurSnoop& Z = h->snoop;
+    const SchurRel& R = h->rel;
+    SchurSnoopView W{};
+    W.n = V.n; W.L = V.L; W.m = V.m;
+    W.lm_ptr = V.lm_ptr; W.row_pose = V.row_pose; W.row_lm = V.row_lm; W.pose_ptr = V.pose_ptr; W.pose_rows = V.pose_rows;
+    W.row_w = const_cast<double*>(V.row_w);
+    W.wt = R.wt; W.lmwt = R.lmwt; W.fit = R.fit;
+    W.saved = Z.saved; W.row_mask = Z.row_mask; W.lm_mask = Z.lm_mask;
+    W.lm_dec = Z.lm_dec; W.pose_pick = Z.pose_pick; W.pose_short = Z.pose_short; W.pose_out = Z.pose_out; W.lm_out = Z.lm_out;
+    W.crit_used = Z.crit_used;
+    return W;
+}
+
+int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
+                    int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (!(crit >= 0.0)) return sfail(VBA_EINVAL, "crit must be >= 0 (+inf rejects nothing)");
+    if (min_rows < 0 || min_track < 0) return sfail(VBA_EINVAL, "min_rows and min_track must be >= 0");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    if (int rc = schur_query_index(h)) return rc;
+    if (int rc = schur_rel_alloc(h)) return rc;
+    if (int rc = schur_snoop_alloc(h)) return rc;
+    SchurSnoop& Z = h->snoop;
+    hipStream_t s = h->stream;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_rel_device(h, lamda, Z.ev[0], V, &bad)) return rc;
+    *info = bad;
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    if (bad != 0) {                 // no factor, no test: nothing is rejected; the critical value of a fit that does not exist
+        SCHK(hipEventRecord(Z.ev[1], s));
+        SCHK(hipStreamSynchronize(s));
+        (void)hipEventElapsedTime(&Z.ms, Z.ev[0], Z.ev[1]);
+        if (crit_used) *crit_used = scaled ? std::nan("") : crit;
+        return VBA_OK;
+    }
+    const SchurSnoopView W = schur_snoop_view(h);
+    schur_snoop_launch(W, crit, scaled ? 1 : 0, min_rows, min_track, s);
+    SCHK(hipEventRecord(Z.ev[1], s));
+    SCHK(hipGetLastError());
+    std::vector<int> out;
+    try {
+        out.resize((size_t)V.n + (size_t)V.L);
+    } catch (const std::bad_alloc&) {
+        return sfail(VBA_ENOMEM, "host staging for the counts of vba_schur_snoop failed");
+    }
+    double c = 0.0;
+    SCHK(hipMemcpyAsync(out.data(), Z.pose_out, (size_t)V.n * 4, hipMemcpyDeviceToHost, s));
+    SCHK(hipMemcpyAsync(out.data() + V.n, Z.lm_out, (size_t)V.L * 4, hipMemcpyDeviceToHost, s));
+    SCHK(hipMemcpyAsync(&c, Z.crit_used, 8, hipMemcpyDeviceToHost, s));
+    SCHK(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&Z.ms, Z.ev[0], Z.ev[1]);
+    int now[3] = {0, 0, 0};
+    for (int i = 0; i < V.n; ++i) now[0] += out[i];
+    for (int l = 0; l < V.L; ++l)
+        if (out[(size_t)V.n + l] > 0) { now[1] += 1; now[2] += out[(size_t)V.n + l] - 1; }
+    for (int k = 0; k < 3; ++k) {
+        Z.totals[k] += now[k];
+        if (counts) counts[k] = now[k];
+    }
+    if (crit_used) *crit_used = c;
+    return VBA_OK;
+}
+
+int vba_schur_rejected(vba_schur_handle h, unsigned char* row_mask, unsigned char* lm_mask, int* totals) {
+    if (!h) return sfail(VBA_EINVAL, "null handle");
+    const SchurSnoop& Z = h->snoop;
+    if (totals) for (int k = 0; k < 3; ++k) totals[k] = Z.arena ? Z.totals[k] : 0;
+    if (!Z.arena) {
+        if (row_mask) std::memset(row_mask, 0, (size_t)h->V.m);
+        if (lm_mask) std::memset(lm_mask, 0, (size_t)h->V.L);
+        return VBA_OK;
+    }
+    SCHK(hipSetDevice(h->device));
+    SCHK(hipStreamSynchronize(h->stream));
+    if (row_mask) SCHK(hipMemcpy(row_mask, Z.row_mask, (size_t)h->V.m, hipMemcpyDeviceToHost));
+    if (lm_mask) SCHK(hipMemcpy(lm_mask, Z.lm_mask, (size_t)h->V.L, hipMemcpyDeviceToHost));
+    return VBA_OK;
+}
+
+int vba_schur_snoop_restore(vba_schur_handle h) {
+    if (!h) return sfail(VBA_EINVAL, "null handle");
+    SchurSnoop& Z = h->snoop;
+    if (!Z.arena || (Z.totals[0] == 0 && Z.totals[1] == 0 && Z.totals[2] == 0)) return VBA_OK;
+    SCHK(hipSetDevice(h->device));
+    schur_snoop_restore_launch(schur_snoop_view(h), h->stream);
+    SCHK(hipGetLastError());
+    SCHK(hipMemsetAsync(Z.lm_mask, 0, (size_t)h->V.L, h->stream));
+    SCHK(hipStreamSynchronize(h->stream));
+    std::fill(Z.totals, Z.totals + 3, 0);
+    return VBA_OK;
+}
+
+int vba_schur_last_snoop_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->snoop.ms;
     return VBA_OK;
 }
 

@@ -214,8 +214,63 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_reliability_ms(self.h, byref(v)))
         return v.value
 
-    def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10):
-        """Levenberg-Marquardt driver: damping x10 on a rejected trial, /10 on an accepted one.  Returns the cost history."""
+    def snoop(self, lamda=0.0, crit=3.29, scaled=True, min_rows=6, min_track=3, strict=True):
+        """``vba_schur_snoop`` at the resident state (``include/vinsat_ba.h`` states the rule): the device part of
+        :meth:`reliability`, then at most one rejection per group, on the device.  A rejected row gets weight 0 in place; a
+        rejected catalogue entry leaves the window (every weighted row of the landmark gets weight 0; its prior holds it at
+        ``X0``).  ``crit`` is in units of the w-test, times ``sqrt(s0sq)`` of the device's own fit with ``scaled``; a pose keeps
+        at least ``min_rows`` weighted rows, and a catalogue entry is only tested on tracks of at least ``min_track`` weighted
+        rows.  Returns a dict: ``rows`` (rejected by their own test), ``landmarks``, ``rows_via_landmarks`` of THIS call,
+        ``crit_used``, ``info``.  :meth:`rejected` gives the cumulative masks, :meth:`restore_rejected` undoes everything.
+
+        ``strict`` as in :meth:`reliability`: a system that is not positive definite raises, or rejects nothing and tells ``info``."""
+        counts, used, info = (c_int * 3)(), c_double(), c_int()
+        self._check(self.lib.vba_schur_snoop(self.h, float(lamda), float(crit), int(bool(scaled)), int(min_rows), int(min_track), counts,
+                                             byref(used), byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur snoop: the reduced camera system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        return dict(rows=counts[0], landmarks=counts[1], rows_via_landmarks=counts[2], crit_used=used.value, info=info.value)
+
+    def rejected(self):
+        """``(row_mask [m] bool in the CALLER's row order, landmark_mask [L] bool)``: everything :meth:`snoop` rejected on this
+        handle so far (rows of rejected landmarks included in the row mask)."""
+        rows, lms = np.zeros(self.m, dtype=np.uint8), np.zeros(self.L, dtype=np.uint8)
+        self._check(self.lib.vba_schur_rejected(self.h, rows.ctypes.data_as(c_void_p), lms.ctypes.data_as(c_void_p), None))
+        back = np.zeros(self.m, dtype=bool)
+        back[self.order] = rows != 0                    # device rows are sorted by landmark
+        return back, lms != 0
+
+    def restore_rejected(self):
+        """The weights :meth:`snoop` zeroed come back and both masks are cleared: the handle behaves as one that never snooped."""
+        self._check(self.lib.vba_schur_snoop_restore(self.h))
+
+    def last_snoop_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_snoop_ms(self.h, byref(v)))
+        return v.value
+
+    def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10, snoop=None):
+        """Levenberg-Marquardt driver: damping x10 on a rejected trial, /10 on an accepted one.  Returns the cost history.
+
+        ``snoop = dict(crit=, scaled=, min_rows=, min_track=, rounds=8)`` (any subset; ``lamda=`` of the query too, 0 by default):
+        after the loop ends, at most ``rounds`` rounds of :meth:`snoop`; a round that rejected something is followed by the LM loop again from the
+        resident state, one that rejected nothing ends the rounds.  The history gains one entry per round, ``("snoop", dict of
+        :meth:`snoop`)``."""
+        hist = self._lm_loop(lamda0, max_iters, tol)
+        if snoop is None:
+            return hist
+        opts = dict(snoop)
+        rounds = int(opts.pop("rounds", 8))
+        for _ in range(rounds):
+            res = self.snoop(**opts)
+            hist.append(("snoop", res))
+            if res["rows"] + res["landmarks"] == 0:
+                break
+            hist += self._lm_loop(lamda0, max_iters, tol)
+        return hist
+
+    def _lm_loop(self, lamda0, max_iters, tol):
         lam, hist = float(lamda0), []
         for _ in range(max_iters):
             c0, c1, ok = self.iterate(lam)
