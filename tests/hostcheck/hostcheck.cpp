@@ -85,6 +85,68 @@ void hc_assemble(int n, const double* Hraw, const double* braw, double inv_wmax,
     }
 }
 
+// BA_reg: the same rows with the per-pose prior (prior_H [n,36], prior_x [n,6] = prior position / velocity); the prior residual is
+// staged as asm_input<true> stages it (vba_asm.h: one multiplication, five fma)
+void hc_assemble_reg(int n, const double* Hraw, const double* braw, double inv_wmax, double sigma, const double* Phi,
+                     const double* rorb, const double* qgrad, const double* Hd, const double* Hu, const double* Hl,
+                     const double* prior_H, const double* prior_x, const double* states, double* bands, double* rhs) {
+    for (int i = 0; i < n; ++i) {
+        AsmRow R{};
+        R.Hraw = Hraw + 21 * i; R.braw = braw + 6 * i; R.inv_wmax = inv_wmax; R.sigma = sigma;
+        R.Phi_i = i < n - 1 ? Phi + 36 * i : nullptr;
+        R.Phi_im1 = i > 0 ? Phi + 36 * (i - 1) : nullptr;
+        R.rorb_i = i < n - 1 ? rorb + 6 * i : nullptr;
+        R.rorb_im1 = i > 0 ? rorb + 6 * (i - 1) : nullptr;
+        R.qgrad = qgrad + 3 * i; R.Hd = Hd + 9 * i; R.Hu = Hu + 9 * i; R.Hl = Hl + 9 * i;
+        double pr[6];
+        const double* xp = prior_x + 6 * i;
+        const double* st = states + 10 * i;
+        for (int a = 0; a < 6; ++a) {
+            const double* Hr = prior_H + 36 * i + 6 * a;
+            double r = vba_mul(Hr[0], xp[0] - st[0]);
+            r = fma(Hr[1], xp[1] - st[1], r);
+            r = fma(Hr[2], xp[2] - st[2], r);
+            r = fma(Hr[3], xp[3] - st[7], r);
+            r = fma(Hr[4], xp[4] - st[8], r);
+            pr[a] = fma(Hr[5], xp[5] - st[9], r);
+        }
+        R.prior_H = prior_H + 36 * i; R.prior_r = pr;
+        for (int w = 0; w < 3; ++w)
+            for (int a = 0; a < 9; ++a)
+                for (int b = 0; b < 9; ++b) bands[((i * 3 + w) * 9 + a) * 9 + b] = band_entry(R, w, a, b);
+        for (int a = 0; a < 9; ++a) rhs[9 * i + a] = rhs_entry(R, a);
+    }
+}
+
+// sum |r_prior| of one pose as the dynamics kernels form it (prior_residual)
+void hc_prior_residual(int n, const double* prior_H, const double* prior_x, const double* states, double* r) {
+    for (int i = 0; i < n; ++i) prior_residual(prior_H + 36 * i, prior_x + 6 * i, states + 10 * i, r + 6 * i);
+}
+
+// Landmark-only step of one pose: the closed form of step_blockdiag6 (vba_step.h, a device-only header): (H / w_max + lam32 I) x =
+// b / w_max by Gauss-Jordan without row exchanges, velocity rows zero; the device's fast reciprocal is a division here.
+void hc_step6(int n, const double* Hraw, const double* braw, double inv_wmax, double lam32, double* dpose) {
+    for (int i = 0; i < n; ++i) {
+        const double* H = Hraw + 21 * i;
+        const double* b = braw + 6 * i;
+        double A[6][7];
+        for (int a = 0; a < 6; ++a) {
+            for (int c = 0; c < 6; ++c) A[a][c] = H[sym6(a, c)] * inv_wmax + (a == c ? lam32 : 0.0);
+            A[a][6] = b[a] * inv_wmax;
+        }
+        for (int k = 0; k < 6; ++k) {
+            const double inv = 1.0 / A[k][k];
+            for (int c = 0; c < 7; ++c) A[k][c] *= inv;
+            for (int r = 0; r < 6; ++r)
+                if (r != k) {
+                    const double f = A[r][k];
+                    for (int c = 0; c < 7; ++c) A[r][c] -= f * A[k][c];
+                }
+        }
+        for (int r = 0; r < 9; ++r) dpose[9 * i + r] = r < 6 ? A[r][6] : 0.0;
+    }
+}
+
 // the plan of a long gap (vba_long.hip) for each of n step counts: L, P, sub, nsubL, G and the pool states the upload reserves
 void hc_long_plan(int64_t n, const int64_t* s, int64_t* out /*[n,6]*/) {
     for (int64_t k = 0; k < n; ++k) {
