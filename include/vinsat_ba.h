@@ -592,7 +592,7 @@ int vba_prepare_rows(int device, int64_t M, const double* det /*[M,6]*/, const i
  * The reference keeps its landmarks fixed (BA_filtering.py:32-37) and has nothing to marginalise; this mode is the
  * variant BASELINE.json's north_star describes on top of it and has NO counterpart in the reference.  Unknowns: 6 per
  * pose (position, rotation; velocities untouched) and 3 per landmark, the landmarks held by a catalogue prior
- * N(X0, sigma_prior^2 I); weights = confidences (the reference's alpha = 2 case).  One call of vba_schur_iterate builds the
+ * N(X0, sigma_prior^2 I); weights = confidences (the reference's alpha = 2 case) until vba_schur_reweight is called.  One call of vba_schur_iterate builds the
  * normal equations at the resident state, marginalises the landmarks (3x3 inversions), factorises the dense reduced
  * camera system on the matrix cores (blocked Cholesky), back-substitutes, and keeps the step if the cost
  * sum w |r|^2 + |X - X0|^2 / sigma^2 went down.  Validated against oracle/schur_oracle.py (this repository's own CPU
@@ -621,7 +621,8 @@ int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, dou
 int vba_schur_last_info(vba_schur_handle h, int* info);
 /* HIP-event times of the last iterate: build (blocks + Schur complement), factor (Cholesky), solve (substitutions + update) */
 int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, float* solve_ms);
-/* what = 0: the step of the last iterate [6 n + 3 L]; 1: its Cholesky factor, dense lower triangular [6n, 6n] */
+/* what = 0: the step of the last iterate [6 n + 3 L]; 1: its Cholesky factor, dense lower triangular [6n, 6n]; 2: the 2 m keys
+ * |r| of the last vba_schur_reweight, sorted row order, row by row, u before v (VBA_ESTATE if none since the upload) */
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity);
 /* Covariances of the free-landmark system at the resident state: blocks of the inverse of H = [[B, E], [E^T, C]] as
  * vba_schur_iterate(h, lamda, ...) would build it there (lamda on every diagonal entry of B and C; lamda = 0, the usual
@@ -710,6 +711,44 @@ int vba_schur_rejected(vba_schur_handle h, unsigned char* row_mask /*[m] or NULL
 int vba_schur_snoop_restore(vba_schur_handle h);
 /* HIP-event time of the last vba_schur_snoop on this handle (the reliability query's device part and the passes of the rule) */
 int vba_schur_last_snoop_ms(vba_schur_handle h, float* ms);
+/* Robust re-weighting of the free-landmark fit: the reference's weights (BA_filtering.py:21-25) at the resident state, written
+ * into the handle's weight array in place, on the device.  The reference computes them once per BA() call and holds them through
+ * its LM trials; here the caller decides when (vinsat_amd/schur.py: solve(robust=...)).
+ *   r_k = uv_k - est_k at the resident state, the projection of the cost kernel of vba_schur_iterate (Z_MIN clamp included).
+ *   Keys: |r|, two per row, of ALL rows whatever their weight: a row of weight 0 (rejected, or uploaded so) counts in the median,
+ *   as a row of confidence 0 does in the reference (BA_filtering.py:23).
+ *   c = *c_obs = the exact lower median, the key of rank (2 m - 1) / 2 (torch.median), by a radix select on the bit patterns: the
+ *   bits of the sorted keys' entry of that rank.
+ *   q_k = mean over the two components of ((r / c)^2 / |alpha - 2| + 1)^(alpha / 2 - 1) / c^2;  *w_max = q_max = the largest q_k over
+ *   all rows, taken before the base weights enter (BA_filtering.py:25);  rho_k = q_k / q_max.
+ *   alpha in [1, 2]; anything else, or NaN: VBA_EINVAL.  alpha == 2 is the reference's inf ** 0 == 1: rho_k is exactly 1, no power is
+ *   evaluated (q_max = 1 / c^2); c_obs is still computed and returned.
+ *   base_k = the weight of row k as vba_schur_upload received it.  A row that is not rejected: row_w[k] = rho_k * base_k, one
+ *   product.  A row vba_schur_snoop has rejected keeps 0.0 and its saved weight becomes rho_k * base_k: vba_schur_snoop_restore
+ *   then yields the handle that never snooped and was re-weighted at this state.
+ * *status = 0: re-weighted.  *status = 1: c_obs is 0 or not finite (a NaN residual among the middle keys, a state that fits
+ * exactly), or q_max is not positive and finite (a NaN residual anywhere: numpy's max); then weights and saved values are
+ * untouched, *c_obs holds what was found, *w_max is NaN and the call still returns VBA_OK.
+ * From the call's return the handle gives, bit for bit, what a fresh handle gives that was uploaded with the same structure, the
+ * weights vba_schur_get_weights now returns, and the same state (vba_schur_iterate, vba_schur_covariance, vba_schur_reliability,
+ * vba_schur_snoop).  vba_schur_reweight(h, 2.0, ...) puts base back bit for bit on the rows that are not rejected.  State,
+ * last_info, last_ms, debug_fetch(0 / 1), last_covariance_ms, last_reliability_ms and last_snoop_ms read as before the call.
+ * The feature's state (base weights, keys and raw weights: four doubles per row; the select's histograms) is allocated by the
+ * first re-weighting of a handle and lives until vba_schur_upload, which clears it: those are new weights.  A handle that never
+ * calls this allocates nothing.  Synchronous.  No float atomics (integer atomics count the select's histograms, which is exact in
+ * any order; the maximum has one fixed shape): equal problems give equal bits, across calls and across handles.
+ * Errors: VBA_EINVAL (null argument, alpha); VBA_ESTATE before upload or before a state is set; VBA_ENOMEM: no room for the state. */
+int vba_schur_reweight(vba_schur_handle h, double alpha, double* c_obs, double* w_max, int* status);
+/* The current weights and the base weights (as uploaded), both in sorted row order.  On a handle that never re-weighted base
+ * equals w, except that rows the snoop rejected report their saved value.  Either output may be NULL. */
+int vba_schur_get_weights(vba_schur_handle h, double* w /*[m] or NULL*/, double* base /*[m] or NULL*/);
+/* HIP-event time of the last vba_schur_reweight on this handle (keys, select, raw weights, scaling) */
+int vba_schur_last_reweight_ms(vba_schur_handle h, float* ms);
+/* The select of vba_schur_reweight on caller keys: *median = the key of rank (count - 1) / 2 among count >= 1 non-negative
+ * doubles (+0, denormals and +inf included), bit for bit the entry of that rank of the sorted keys.  It runs the same select
+ * kernels (one workgroup up to 8192 keys, eight histogram passes beyond), on a process-wide workspace as vba_prepare_rows does,
+ * and restores the caller's HIP device.  VBA_EINVAL: a NaN key, a key with the sign bit set (-0 included), count < 1 or > 2^31. */
+int vba_schur_median(int device, const double* keys, int64_t count, double* median);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@
 //
 // Reprojection and its pose Jacobian are the reference's (vba_math.h: BA_utils.py:30-49); the landmark Jacobian is
 // d uv / d X = A R^T = -(translation part of the pose Jacobian).  Weights are the observation confidences (the
-// reference's alpha = 2 case, BA_filtering.py:22-25, where the robust weight is constant).
+// reference's alpha = 2 case, BA_filtering.py:22-25, where the robust weight is constant) until vba_schur_reweight is called.
 //
 // Kernels (all reductions in a fixed order -- no float atomics):
 //   k_lm_blocks     thread per landmark: C_l, w_l over its rows, C_l^-1, then E_k and Y_k = E_k C_l^-1 per row
@@ -34,9 +34,11 @@
 //   k_rel_stats     thread per landmark / per pose: their rows' statistics; the catalogue prior of a landmark as an observation
 //   k_rel_totals    one block: cost, redundancy, variance factor, largest tests (strided partial sums, one tree)
 // Data snooping (vba_schur_snoop: the device part of the reliability query, then the passes of vba_schur_snoop.hip)
+// Robust re-weighting (vba_schur_reweight, vba_schur_median: the passes of vba_schur_robust.hip)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -46,6 +48,7 @@
 #include "../../include/vinsat_ba.h"
 #include "vba_math.h"
 #include "vba_schur_rel_math.h"
+#include "vba_schur_robust.h"
 #include "vba_schur_snoop.h"
 
 namespace {
@@ -1071,6 +1074,28 @@ struct SchurSnoop {
     float ms = 0.0f;
 };
 
+// State of vba_schur_reweight, allocated by the first re-weighting of a handle and cleared by vba_schur_upload: the weights as
+// uploaded, the 2 m keys |r| and the raw weights of the last call, the select's histograms, two timing events.
+struct SchurRobust {
+    char* arena = nullptr;
+    double *base = nullptr, *keys = nullptr, *q = nullptr, *part = nullptr, *res = nullptr;
+    unsigned long long *hist = nullptr, *state = nullptr;
+    hipEvent_t ev[2] = {};
+    bool captured = false;      // base holds the weights of the current upload
+    bool have_keys = false;     // keys are those of a re-weighting since the current upload
+    int launches = 0;           // kernel launches of the last re-weighting
+    float ms = 0.0f;
+};
+
+// one grow-only workspace per process for vba_schur_median (keys, the select's scratch, the result)
+struct MedianWorkspace {
+    std::mutex m;
+    int device = -1;
+    char* base = nullptr;
+    size_t size = 0;
+    hipStream_t stream = nullptr;
+} g_median_ws;
+
 thread_local std::string g_serr;
 int sfail(int code, const std::string& msg) { g_serr = msg; return code; }
 
@@ -1103,6 +1128,7 @@ struct vba_schur_context {
     SchurQuery q;               // vba_schur_covariance's scratch (nothing until the first query)
     SchurRel rel;               // vba_schur_reliability's scratch on top of it (nothing until the first reliability query)
     SchurSnoop snoop;           // vba_schur_snoop's state (nothing until the first snoop)
+    SchurRobust robust;         // vba_schur_reweight's state (nothing until the first re-weighting)
     int bw = 1 << 30;           // tile bandwidth of the reduced system (max |I - J| over its non-zero tiles), from the block list
 };
 
@@ -1174,6 +1200,8 @@ int vba_schur_destroy(vba_schur_handle h) {
     for (hipEvent_t e : h->q.ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : h->rel.ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : h->snoop.ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : h->robust.ev) if (e) hipEventDestroy(e);
+    if (h->robust.arena) hipFree(h->robust.arena);
     if (h->snoop.arena) hipFree(h->snoop.arena);
     if (h->rel.arena) hipFree(h->rel.arena);
     if (h->q.arena) hipFree(h->q.arena);
@@ -1225,6 +1253,7 @@ int vba_schur_upload(vba_schur_handle h, const int* lm_ptr, const int* row_pose,
         SCHK(hipStreamSynchronize(nullptr));
         std::fill(h->snoop.totals, h->snoop.totals + 3, 0);
     }
+    h->robust.captured = h->robust.have_keys = false;       // new weights: they are the base of the next re-weighting
     h->uploaded = true;
     return VBA_OK;
 }
@@ -1705,6 +1734,158 @@ int vba_schur_last_snoop_ms(vba_schur_handle h, float* ms) {
     return VBA_OK;
 }
 
+// first re-weighting of a handle: its state and its two timing events
+static int schur_robust_alloc(vba_schur_handle h) {
+    SchurRobust& Z = h->robust;
+    if (Z.arena) return VBA_OK;
+    const size_t m = (size_t)h->V.m;
+    size_t bytes = 0;
+    auto need = [&](size_t b) { size_t o = bytes; bytes += (b + 255) & ~size_t(255); return o; };
+    const size_t o_b = need(m * 8), o_k = need(m * 16), o_q = need(m * 8), o_p = need((size_t)kRobustMaxBlocks * 8), o_r = need(16),
+                 o_s = need(schur_select_scratch_bytes());
+    char* A = nullptr;
+    if (hipMalloc(&A, bytes) != hipSuccess) { (void)hipGetLastError(); return sfail(VBA_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes of re-weighting state failed"); }
+    hipEvent_t ev[2] = {};
+    if (hipMemset(A, 0, bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess || hipEventCreate(&ev[0]) != hipSuccess ||
+        hipEventCreate(&ev[1]) != hipSuccess) {
+        if (ev[0]) hipEventDestroy(ev[0]);
+        hipFree(A);
+        return sfail(VBA_EHIP, "re-weighting state: hipMemset / event creation failed");
+    }
+    Z.arena = A; Z.ev[0] = ev[0]; Z.ev[1] = ev[1];
+    Z.base = (double*)(A + o_b); Z.keys = (double*)(A + o_k); Z.q = (double*)(A + o_q); Z.part = (double*)(A + o_p); Z.res = (double*)(A + o_r);
+    Z.hist = (unsigned long long*)(A + o_s); Z.state = Z.hist + (size_t)kSelPasses * kSelBins;
+    Z.captured = Z.have_keys = false;
+    return VBA_OK;
+}
+
+static SchurRobustView schur_robust_view(vba_schur_handle h) {
+    const SchurView& V = h->V;
+    const SchurRobust& Z = h->robust;
+    SchurRobustView W{};
+    W.n = V.n; W.L = V.L; W.m = V.m;
+    W.row_pose = V.row_pose; W.row_lm = V.row_lm; W.row_u = V.row_u; W.row_v = V.row_v; W.intr = V.intr;
+    W.states = h->S0; W.X = h->X0buf;
+    W.row_w = const_cast<double*>(V.row_w);
+    W.saved = h->snoop.arena ? h->snoop.saved : nullptr;
+    W.row_mask = h->snoop.arena ? h->snoop.row_mask : nullptr;
+    W.base = Z.base; W.keys = Z.keys; W.q = Z.q; W.part = Z.part; W.res = Z.res;
+    W.sel.keys = reinterpret_cast<const unsigned long long*>(Z.keys); W.sel.count = 2 * V.m;
+    W.sel.hist = Z.hist; W.sel.state = Z.state; W.sel.out = Z.res;
+    return W;
+}
+
+int vba_schur_reweight(vba_schur_handle h, double alpha, double* c_obs, double* w_max, int* status) {
+    if (!h || !c_obs || !w_max || !status) return sfail(VBA_EINVAL, "null argument");
+    if (!(alpha >= 1.0 && alpha <= 2.0)) return sfail(VBA_EINVAL, "alpha must lie in [1, 2]");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_robust_alloc(h)) return rc;
+    SchurRobust& Z = h->robust;
+    hipStream_t s = h->stream;
+    const SchurRobustView W = schur_robust_view(h);
+    if (!Z.captured) {
+        schur_robust_capture_launch(W, s);
+        SCHK(hipGetLastError());
+        Z.captured = true;
+    }
+    SCHK(hipEventRecord(Z.ev[0], s));
+    Z.launches = schur_robust_launch(W, alpha, s);
+    SCHK(hipEventRecord(Z.ev[1], s));
+    SCHK(hipGetLastError());
+    double res[2] = {0.0, 0.0};
+    SCHK(hipMemcpyAsync(res, Z.res, 16, hipMemcpyDeviceToHost, s));
+    SCHK(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&Z.ms, Z.ev[0], Z.ev[1]);
+    Z.have_keys = true;
+    const bool ok = res[0] > 0.0 && std::isfinite(res[0]) && res[1] > 0.0 && std::isfinite(res[1]);     // (the test of k_schur_robust_scale)
+    *c_obs = res[0];
+    *w_max = ok ? res[1] : std::nan("");
+    *status = ok ? 0 : 1;
+    return VBA_OK;
+}
+
+int vba_schur_get_weights(vba_schur_handle h, double* w, double* base) {
+    if (!h) return sfail(VBA_EINVAL, "null handle");
+    if (!h->uploaded) return sfail(VBA_ESTATE, "upload the problem first");
+    SCHK(hipSetDevice(h->device));
+    SCHK(hipStreamSynchronize(h->stream));
+    const size_t m = (size_t)h->V.m;
+    if (w) SCHK(hipMemcpy(w, h->V.row_w, m * 8, hipMemcpyDeviceToHost));
+    if (!base) return VBA_OK;
+    if (h->robust.arena && h->robust.captured) {
+        SCHK(hipMemcpy(base, h->robust.base, m * 8, hipMemcpyDeviceToHost));
+        return VBA_OK;
+    }
+    SCHK(hipMemcpy(base, h->V.row_w, m * 8, hipMemcpyDeviceToHost));
+    if (h->snoop.arena) {           // never re-weighted: the weights in place, a rejected row by its saved value
+        std::vector<double> saved;
+        std::vector<unsigned char> mask;
+        try {
+            saved.resize(m);
+            mask.resize(m);
+        } catch (const std::bad_alloc&) {
+            return sfail(VBA_ENOMEM, "host staging for vba_schur_get_weights failed");
+        }
+        SCHK(hipMemcpy(saved.data(), h->snoop.saved, m * 8, hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(mask.data(), h->snoop.row_mask, m, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < m; ++k) if (mask[k]) base[k] = saved[k];
+    }
+    return VBA_OK;
+}
+
+int vba_schur_last_reweight_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->robust.ms;
+    return VBA_OK;
+}
+
+int vba_schur_median(int device, const double* keys, int64_t count, double* median) {
+    if (!keys || !median) return sfail(VBA_EINVAL, "null argument");
+    if (count < 1 || count > (int64_t)1 << 31) return sfail(VBA_EINVAL, "count must lie in [1, 2^31]");
+    for (int64_t k = 0; k < count; ++k)
+        if (std::isnan(keys[k]) || std::signbit(keys[k])) return sfail(VBA_EINVAL, "keys must be non-negative doubles (no NaN, no sign bit)");
+    int cnt = 0, prev = -1;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0) return sfail(VBA_ENODEV, "no HIP device visible");
+    if (device < 0 || device >= cnt) return sfail(VBA_EINVAL, "device index out of range");
+    std::lock_guard<std::mutex> lk(g_median_ws.m);
+    MedianWorkspace& G = g_median_ws;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    struct Back {                   // the caller's HIP device, whatever happens below
+        int dev;
+        ~Back() { if (dev >= 0) (void)hipSetDevice(dev); }
+    } back{prev};
+    SCHK(hipSetDevice(device));
+    const size_t kb = ((size_t)count * 8 + 255) & ~size_t(255), sb = (schur_select_scratch_bytes() + 255) & ~size_t(255);
+    const size_t need = kb + sb + 256;
+    if (G.device != device || G.size < need) {
+        if (G.base) (void)hipFree(G.base);
+        G.base = nullptr;
+        G.size = 0;
+        if (!G.stream || G.device != device) {
+            if (G.stream) (void)hipStreamDestroy(G.stream);
+            G.stream = nullptr;
+            G.device = -1;
+            SCHK(hipStreamCreateWithFlags(&G.stream, hipStreamNonBlocking));
+        }
+        if (hipMalloc(&G.base, need + need / 2) != hipSuccess) { (void)hipGetLastError(); G.base = nullptr; return sfail(VBA_ENOMEM, "hipMalloc of the median workspace failed"); }
+        G.size = need + need / 2;
+        G.device = device;
+    }
+    SchurSelectView W{};
+    W.keys = reinterpret_cast<const unsigned long long*>(G.base);
+    W.count = count;
+    W.hist = reinterpret_cast<unsigned long long*>(G.base + kb);
+    W.state = W.hist + (size_t)kSelPasses * kSelBins;
+    W.out = reinterpret_cast<double*>(G.base + kb + sb);
+    SCHK(hipMemcpyAsync(G.base, keys, (size_t)count * 8, hipMemcpyHostToDevice, G.stream));
+    schur_select_launch(W, G.stream, nullptr);
+    SCHK(hipGetLastError());
+    SCHK(hipMemcpyAsync(median, W.out, 8, hipMemcpyDeviceToHost, G.stream));
+    SCHK(hipStreamSynchronize(G.stream));
+    return VBA_OK;
+}
+
 int vba_schur_last_info(vba_schur_handle h, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
     *info = h->last_info;
@@ -1720,7 +1901,7 @@ int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, flo
 }
 
 // what: 0 = step of the last iteration [6 n + 3 L] (dc then dl), 1 = lower triangle of the Cholesky factor as a dense
-// [6n][6n] row-major matrix (upper part zero)
+// [6n][6n] row-major matrix (upper part zero), 2 = the 2 m keys |r| of the last re-weighting
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity) {
     if (!h || !out) return sfail(VBA_EINVAL, "null argument");
     SCHK(hipSetDevice(h->device));
@@ -1738,6 +1919,12 @@ int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t cap
         SCHK(hipMemcpy(tmp.data(), V.S, tmp.size() * 8, hipMemcpyDeviceToHost));
         for (int r = 0; r < V.N; ++r)
             for (int c = 0; c < V.N; ++c) out[(size_t)r * V.N + c] = c <= r ? tmp[(size_t)r * V.Npad + c] : 0.0;
+        return VBA_OK;
+    }
+    if (what == 2) {
+        if (!h->robust.arena || !h->robust.have_keys) return sfail(VBA_ESTATE, "no re-weighting since the upload");
+        if (capacity < 2 * V.m) return sfail(VBA_EINVAL, "buffer too small");
+        SCHK(hipMemcpy(out, h->robust.keys, (size_t)V.m * 16, hipMemcpyDeviceToHost));
         return VBA_OK;
     }
     return sfail(VBA_EINVAL, "unknown selector");

@@ -25,6 +25,24 @@ from ._lib import PD
 FIT_NAMES = ("omega", "m_eff", "t_rows", "t_prior", "rho", "s0sq", "max_wtest", "max_lm_wtest")
 
 
+def alpha_schedule(it):
+    """The reference's robustness schedule (``BA_filtering.py:22``): 2 for the first calls, 1 from the fifth on."""
+    return min(max(1 - (2 * (it / 5) - 1), 1), 2)
+
+
+def median(keys, device=0):
+    """``vba_schur_median``: the lower median (rank ``(count - 1) // 2``) of non-negative float64 keys by the select kernels of
+    :meth:`SchurBA.reweight`, bit for bit ``numpy.sort(keys)[(count - 1) // 2]``."""
+    lib = _lib.load()
+    k = np.ascontiguousarray(keys, dtype=np.float64).reshape(-1)
+    out = c_double()
+    rc = lib.vba_schur_median(int(device), k.ctypes.data_as(PD), k.size, byref(out))
+    if rc != 0:
+        msg = lib.vba_schur_last_error()
+        raise _lib.VbaError(f"libvinsat_ba (schur) error {rc}: {msg.decode() if msg else ''}")
+    return out.value
+
+
 def build_structure(pose_of_row, landmark_of_row, n, L):
     """Static index structure of a window (see ``include/vinsat_ba.h``, ``vba_schur_upload``).
 
@@ -250,14 +268,62 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_snoop_ms(self.h, byref(v)))
         return v.value
 
-    def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10, snoop=None):
+    def reweight(self, alpha):
+        """``vba_schur_reweight`` at the resident state (``include/vinsat_ba.h``): the reference's robust weights
+        (``BA_filtering.py:21-25``) times the uploaded weights, written into the handle's weights on the device.  ``alpha`` in
+        ``[1, 2]``; 2 puts the uploaded weights back.  Returns a dict: ``c_obs`` (the exact lower median of the ``2 m`` values
+        ``|r|``, rows of weight 0 included), ``w_max`` (the largest raw weight) and ``status`` (1: ``c_obs`` is 0 or not finite,
+        nothing was changed)."""
+        c, wm, st = c_double(), c_double(), c_int()
+        self._check(self.lib.vba_schur_reweight(self.h, float(alpha), byref(c), byref(wm), byref(st)))
+        return dict(c_obs=c.value, w_max=wm.value, status=st.value)
+
+    def weights(self, base=False):
+        """The current weights -- or, with ``base``, the weights as uploaded -- in the CALLER's row order."""
+        out = np.empty(self.m)
+        self._check(self.lib.vba_schur_get_weights(self.h, None if base else out.ctypes.data_as(PD), out.ctypes.data_as(PD) if base else None))
+        back = np.empty(self.m)
+        back[self.order] = out                          # device rows are sorted by landmark
+        return back
+
+    def reweight_keys(self):
+        """The ``2 m`` keys ``|r|`` of the last :meth:`reweight`, ``[m, 2]`` in the device's SORTED row order (``self.order``)."""
+        out = np.empty(2 * self.m)
+        self._check(self.lib.vba_schur_debug_fetch(self.h, 2, out.ctypes.data_as(PD), out.size))
+        return out.reshape(self.m, 2)
+
+    def last_reweight_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_reweight_ms(self.h, byref(v)))
+        return v.value
+
+    def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10, snoop=None, robust=None):
         """Levenberg-Marquardt driver: damping x10 on a rejected trial, /10 on an accepted one.  Returns the cost history.
+
+        ``robust = dict(outer=8, alpha=None)`` (any subset) replaces the single LM loop by the robust loop: for ``it`` in
+        ``range(outer)``, :meth:`reweight` at ``alpha(it)`` (a callable; ``None``: :func:`alpha_schedule`, the reference's) --
+        the history gains ``("reweight", dict of reweight)`` -- then the LM loop from the resident state on those weights,
+        which stay fixed through its trials as the reference's do through a ``BA()`` call.  A re-weighting with ``status != 0``
+        ends the robust loop.  The ``snoop`` rounds, if given, follow on the final weights.
 
         ``snoop = dict(crit=, scaled=, min_rows=, min_track=, rounds=8)`` (any subset; ``lamda=`` of the query too, 0 by default):
         after the loop ends, at most ``rounds`` rounds of :meth:`snoop`; a round that rejected something is followed by the LM loop again from the
         resident state, one that rejected nothing ends the rounds.  The history gains one entry per round, ``("snoop", dict of
         :meth:`snoop`)``."""
-        hist = self._lm_loop(lamda0, max_iters, tol)
+        if robust is None:
+            hist = self._lm_loop(lamda0, max_iters, tol)
+        else:
+            ropts = dict(robust)
+            outer, alpha = int(ropts.pop("outer", 8)), ropts.pop("alpha", None) or alpha_schedule
+            if ropts:
+                raise ValueError(f"unknown robust options {sorted(ropts)}")
+            hist = []
+            for it in range(outer):
+                res = self.reweight(alpha(it))
+                hist.append(("reweight", res))
+                if res["status"] != 0:
+                    break
+                hist += self._lm_loop(lamda0, max_iters, tol)
         if snoop is None:
             return hist
         opts = dict(snoop)
