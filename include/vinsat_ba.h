@@ -591,7 +591,7 @@ int vba_prepare_rows(int device, int64_t M, const double* det /*[M,6]*/, const i
 /* ---- free-landmark Schur-complement BA: ADD-ON, PARITY UNPINNED ------------------------------------------
  * The reference keeps its landmarks fixed (BA_filtering.py:32-37) and has nothing to marginalise; this mode is the
  * variant BASELINE.json's north_star describes on top of it and has NO counterpart in the reference.  Unknowns: 6 per
- * pose (position, rotation; velocities untouched) and 3 per landmark, the landmarks held by a catalogue prior
+ * pose (position, rotation; velocities untouched unless vba_schur_enable_dynamics adds them) and 3 per landmark, the landmarks held by a catalogue prior
  * N(X0, sigma_prior^2 I); weights = confidences (the reference's alpha = 2 case) until vba_schur_reweight is called.  One call of vba_schur_iterate builds the
  * normal equations at the resident state, marginalises the landmarks (3x3 inversions), factorises the dense reduced
  * camera system on the matrix cores (blocked Cholesky), back-substitutes, and keeps the step if the cost
@@ -621,9 +621,27 @@ int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, dou
 int vba_schur_last_info(vba_schur_handle h, int* info);
 /* HIP-event times of the last iterate: build (blocks + Schur complement), factor (Cholesky), solve (substitutions + update) */
 int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, float* solve_ms);
-/* what = 0: the step of the last iterate [6 n + 3 L]; 1: its Cholesky factor, dense lower triangular [6n, 6n]; 2: the 2 m keys
- * |r| of the last vba_schur_reweight, sorted row order, row by row, u before v (VBA_ESTATE if none since the upload) */
+/* what = 0: the step of the last iterate [6 n + 3 L]; 1: its Cholesky factor, dense lower triangular [6n, 6n] ([9n, 9n] on a handle
+ * with the dynamics factor); 2: the 2 m keys |r| of the last vba_schur_reweight, sorted row order, row by row, u before v (VBA_ESTATE
+ * if none since the upload).  On a handle with the dynamics factor (VBA_ESTATE without it) 3: the velocity step dv [n, 3] of the
+ * last iterate; 4: the residuals r [n - 1, 6] and 5: the Jacobians D Phi [n - 1, 6, 6] of the edges at the state the last iterate
+ * started from; 6: the edges' shares sigma_dyn |r|^2 [n - 1] of the cost there. */
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity);
+/* The orbit-dynamics factor with the velocities as unknowns, opt-in per handle, after vba_schur_upload.  time_idx [n]: the second
+ * of every pose; every gap time_idx[i + 1] - time_idx[i] in 1 .. 64 (the domain of the sequential propagation; longer gaps stay
+ * with the fixed-landmark path).  For every edge i -> i + 1 the reference's residual (BA_utils.py:467-476, 501-509)
+ *   r_i = D (propagate(p_i, v_i; gap one-second RK4 steps of the J2 model) - (p_{i+1}, v_{i+1})),  D = diag(1, 1, 1, 100, 100, 100),
+ * Jacobians D Phi_i at pose i and -D at pose i + 1, weight sigma_dyn, Gauss-Newton (sigma J^T J, -sigma J^T r); the cost gains
+ * sigma_dyn sum |r_i|^2.  No wmax_scale: the rows keep the weights the handle holds.  The ATTITUDE factor of the fixed-landmark
+ * path is not part of this mode: its Newton blocks are not symmetric and the reduced system here is factorised by a Cholesky.
+ * Unknowns become dc [n, 6], dv [n, 3] and dl [L, 3]; the reduced system is ordered [6 n pose | 3 n velocity] unknowns, N = 9 n
+ * (S, g and the factor's arrays are re-sized), lamda goes on the velocity diagonal too, vba_schur_get_state returns the updated
+ * velocities, and the build time of vba_schur_last_ms includes the factor's kernels.  vba_schur_reweight, vba_schur_get_weights
+ * and vba_schur_median work unchanged; vba_schur_covariance, vba_schur_reliability and vba_schur_snoop return VBA_ESTATE on such a
+ * handle (their redundancy counts and gathers assume the 6 n system).  A handle that never calls this behaves as before.
+ * Errors: VBA_EINVAL for n < 2, a gap outside 1 .. 64, a time_idx that does not increase, a sigma_dyn that is not positive and
+ * finite; VBA_ESTATE before the upload or on a handle that has the factor already. */
+int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx /*[n]*/, double sigma_dyn);
 /* Covariances of the free-landmark system at the resident state: blocks of the inverse of H = [[B, E], [E^T, C]] as
  * vba_schur_iterate(h, lamda, ...) would build it there (lamda on every diagonal entry of B and C; lamda = 0, the usual
  * case, gives the undamped covariance -- the catalogue prior fixes the gauge).  With S = B - E C^-1 E^T and Y_k = E_k C_l^-1:

@@ -35,6 +35,8 @@
 //   k_rel_totals    one block: cost, redundancy, variance factor, largest tests (strided partial sums, one tree)
 // Data snooping (vba_schur_snoop: the device part of the reliability query, then the passes of vba_schur_snoop.hip)
 // Robust re-weighting (vba_schur_reweight, vba_schur_median: the passes of vba_schur_robust.hip)
+// Orbit-dynamics factor with velocity unknowns (vba_schur_enable_dynamics: the kernels of vba_schur_dyn.hip; the reduced system
+// becomes [6 n pose | 3 n velocity] unknowns, the kernels of this file fill and factorise it unchanged)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -47,6 +49,8 @@
 
 #include "../../include/vinsat_ba.h"
 #include "vba_math.h"
+#include "vba_schur_dyn.h"
+#include "vba_schur_dyn_math.h"
 #include "vba_schur_rel_math.h"
 #include "vba_schur_robust.h"
 #include "vba_schur_snoop.h"
@@ -63,7 +67,7 @@ constexpr int kPanel = 4;           // tile columns per panel: the trailing upda
 struct SchurView {
     int n, L;
     int64_t m;
-    int N, Npad, nb;                // reduced system: N = 6 n, padded to a multiple of kT, nb tiles per side
+    int N, Npad, nb;                // reduced system: N = 6 n (9 n with the dynamics factor), padded to a multiple of kT, nb tiles per side
     // rows sorted by landmark: CSR lm_ptr[L+1]
     const int* lm_ptr;
     const int* row_pose;            // [m]
@@ -1087,6 +1091,18 @@ struct SchurRobust {
     float ms = 0.0f;
 };
 
+// State of vba_schur_enable_dynamics: the reduced system re-sized for N = 9 n (S, g, ybuf, invL: the view points here from then on),
+// the edges' step counts, the factor of the last build and the partials of its cost.
+struct SchurDyn {
+    char* arena = nullptr;
+    bool enabled = false;
+    double sigma = 0.0;
+    int* steps = nullptr;
+    double *r = nullptr, *A = nullptr, *ecost = nullptr, *part = nullptr;
+    int npart = 0;
+    std::vector<double> h_part;
+};
+
 // one grow-only workspace per process for vba_schur_median (keys, the select's scratch, the result)
 struct MedianWorkspace {
     std::mutex m;
@@ -1095,6 +1111,10 @@ struct MedianWorkspace {
     size_t size = 0;
     hipStream_t stream = nullptr;
 } g_median_ws;
+
+// why the three queries refuse a handle with the dynamics factor
+const char* const kDynRefusal = " is not available on a handle with the dynamics factor: its redundancy counts and gathers assume the "
+                                "6 n reduced system of the reprojection rows";
 
 thread_local std::string g_serr;
 int sfail(int code, const std::string& msg) { g_serr = msg; return code; }
@@ -1129,6 +1149,7 @@ struct vba_schur_context {
     SchurRel rel;               // vba_schur_reliability's scratch on top of it (nothing until the first reliability query)
     SchurSnoop snoop;           // vba_schur_snoop's state (nothing until the first snoop)
     SchurRobust robust;         // vba_schur_reweight's state (nothing until the first re-weighting)
+    SchurDyn dyn;               // vba_schur_enable_dynamics' state (nothing on a handle without the dynamics factor)
     int bw = 1 << 30;           // tile bandwidth of the reduced system (max |I - J| over its non-zero tiles), from the block list
 };
 
@@ -1201,6 +1222,7 @@ int vba_schur_destroy(vba_schur_handle h) {
     for (hipEvent_t e : h->rel.ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : h->snoop.ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : h->robust.ev) if (e) hipEventDestroy(e);
+    if (h->dyn.arena) hipFree(h->dyn.arena);
     if (h->robust.arena) hipFree(h->robust.arena);
     if (h->snoop.arena) hipFree(h->snoop.arena);
     if (h->rel.arena) hipFree(h->rel.arena);
@@ -1246,6 +1268,7 @@ int vba_schur_upload(vba_schur_handle h, const int* lm_ptr, const int* row_pose,
     h->V.inv_sigma2 = 1.0 / (sigma_prior * sigma_prior);
     h->bw = 0;
     for (int b = 0; b < V.nblk; ++b) h->bw = std::max(h->bw, (6 * blk_i[b] + 5) / kT - (6 * blk_j[b]) / kT);
+    if (h->dyn.enabled) h->bw = V.nb - 1;       // velocity rows reach every pose column
     h->q.indexed = false;
     if (h->snoop.arena) {       // new weights: nothing is rejected
         SCHK(hipMemset(h->snoop.row_mask, 0, (size_t)V.m));
@@ -1278,14 +1301,28 @@ int vba_schur_get_state(vba_schur_handle h, double* states, double* landmarks) {
     return VBA_OK;
 }
 
+// the dynamics arrays of a handle with the factor enabled, at the damping of the view
+static SchurDynView schur_dyn_view(vba_schur_handle h, const SchurView& V) {
+    const SchurDyn& D = h->dyn;
+    SchurDynView W{};
+    W.n = V.n; W.Npad = V.Npad; W.sigma = D.sigma; W.lamda = V.lamda;
+    W.steps = D.steps; W.r = D.r; W.A = D.A; W.ecost = D.ecost; W.part = D.part; W.npart = D.npart;
+    W.S = V.S; W.g = V.g;
+    return W;
+}
+
 static int schur_cost(vba_schur_handle h, const double* states, const double* X, double* cost) {
     SchurView V = h->V;
+    SchurDyn& D = h->dyn;
     hipLaunchKernelGGL(k_cost, dim3(V.npart), dim3(256), 0, h->stream, V, states, X);
+    if (D.enabled) schur_dyn_cost_launch(schur_dyn_view(h, V), states, h->stream);
     SCHK(hipGetLastError());
     SCHK(hipMemcpyAsync(h->h_part.data(), V.part, (size_t)V.npart * 8, hipMemcpyDeviceToHost, h->stream));
+    if (D.enabled) SCHK(hipMemcpyAsync(D.h_part.data(), D.part, (size_t)D.npart * 8, hipMemcpyDeviceToHost, h->stream));
     SCHK(hipStreamSynchronize(h->stream));
     double s = 0.0;
     for (int b = 0; b < V.npart; ++b) s += h->h_part[b];      // fixed order
+    if (D.enabled) for (int b = 0; b < D.npart; ++b) s += D.h_part[b];     // ... the dynamics partials after the rows' and the prior's
     *cost = s;
     return VBA_OK;
 }
@@ -1300,6 +1337,11 @@ static int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_
     hipLaunchKernelGGL(k_lm_blocks, dim3((V.L + 255) / 256), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pose_blocks, dim3((V.n + 15) / 16), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pair_blocks, dim3(V.nblk), dim3(64), 0, s, V);
+    if (h->dyn.enabled) {       // the dynamics blocks on top of the reprojection blocks (the queries never come here with the factor on)
+        const SchurDynView W = schur_dyn_view(h, V);
+        schur_dyn_edges_launch(W, V.states, s);
+        schur_dyn_scatter_launch(W, s);
+    }
     if (V.Npad > V.N) hipLaunchKernelGGL(k_pad_identity, dim3((V.Npad - V.N + 63) / 64), dim3(64), 0, s, V);
     if (ev_built) SCHK(hipEventRecord(ev_built, s));
     if (h->classic == 1) {  // round 2: one tile column at a time, trailing update with K = 64 (VBA_SCHUR_CLASSIC=2: panels, round-2 tile kernel)
@@ -1364,6 +1406,7 @@ int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, dou
     for (int kb = V.nb - 1; kb >= 0; --kb)
         hipLaunchKernelGGL(k_trsv_step, dim3(1 + std::min(h->bw, kb)), dim3(256), 0, s, V, kb, 1);
     hipLaunchKernelGGL(k_lm_update, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V);
+    if (h->dyn.enabled) schur_dyn_update_launch(schur_dyn_view(h, V), V.states, V.states_new, s);
     SCHK(hipEventRecord(h->ev[3], s));
     SCHK(hipGetLastError());
     int info = 0;
@@ -1485,6 +1528,7 @@ static int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hi
 
 int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov, double* pair_cov, double* lm_cov, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_covariance") + kDynRefusal);
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
     SCHK(hipSetDevice(h->device));
@@ -1567,6 +1611,7 @@ static int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begi
 int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
                           double* lm_stats, double* pose_stats, double* fit, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_reliability") + kDynRefusal);
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
     SCHK(hipSetDevice(h->device));
@@ -1648,6 +1693,7 @@ static SchurSnoopView schur_snoop_view(vba_schur_handle h) {
 int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
                     int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_snoop") + kDynRefusal);
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!(crit >= 0.0)) return sfail(VBA_EINVAL, "crit must be >= 0 (+inf rejects nothing)");
     if (min_rows < 0 || min_track < 0) return sfail(VBA_EINVAL, "min_rows and min_track must be >= 0");
@@ -1886,6 +1932,54 @@ int vba_schur_median(int device, const double* keys, int64_t count, double* medi
     return VBA_OK;
 }
 
+int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx, double sigma_dyn) {
+    if (!h || !time_idx) return sfail(VBA_EINVAL, "null argument");
+    if (!h->uploaded) return sfail(VBA_ESTATE, "upload the problem first");
+    if (h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is already enabled on this handle");
+    if (!(sigma_dyn > 0.0) || !std::isfinite(sigma_dyn)) return sfail(VBA_EINVAL, "sigma_dyn must be positive and finite");
+    SchurView& V = h->V;
+    const int n = V.n;
+    if (n < 2) return sfail(VBA_EINVAL, "the dynamics factor needs at least two poses");
+    std::vector<int> steps(n - 1);
+    for (int i = 0; i + 1 < n; ++i) {
+        const int64_t d = (int64_t)time_idx[i + 1] - (int64_t)time_idx[i];
+        if (d < 1) return sfail(VBA_EINVAL, "time_idx must increase: poses " + std::to_string(i) + " and " + std::to_string(i + 1));
+        if (d > kSchurDynMaxGap)
+            return sfail(VBA_EINVAL, "a gap of " + std::to_string(d) + " steps between poses " + std::to_string(i) + " and " + std::to_string(i + 1) +
+                                         ": the dynamics factor of this mode covers gaps of 1 .. " + std::to_string(kSchurDynMaxGap) + " steps");
+        steps[i] = (int)d;
+    }
+    SCHK(hipSetDevice(h->device));
+    SCHK(hipStreamSynchronize(h->stream));
+    const int N = 9 * n, nb = (N + kT * kPanel - 1) / (kT * kPanel) * kPanel, Npad = nb * kT;
+    SchurDyn& D = h->dyn;
+    const int npart = schur_dyn_partials(n);
+    size_t bytes = 0;
+    auto need = [&](size_t b) { size_t o = bytes; bytes += (b + 255) & ~size_t(255); return o; };
+    const size_t o_S = need((size_t)Npad * Npad * 8), o_g = need((size_t)Npad * 8), o_y = need((size_t)Npad * 8), o_iL = need((size_t)nb * kT * kT * 8);
+    const size_t o_st = need((size_t)(n - 1) * 4), o_r = need((size_t)(n - 1) * 48), o_A = need((size_t)(n - 1) * 288), o_ec = need((size_t)(n - 1) * 8),
+                 o_part = need((size_t)npart * 8);
+    char* A = nullptr;
+    if (hipMalloc(&A, bytes) != hipSuccess) { (void)hipGetLastError(); return sfail(VBA_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes for the dynamics factor failed"); }
+    if (hipMemset(A, 0, bytes) != hipSuccess || hipMemcpy(A + o_st, steps.data(), (size_t)(n - 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {
+        hipFree(A);
+        return sfail(VBA_EHIP, "dynamics factor: hipMemset / upload failed");
+    }
+    // the scratch of the queries was sized for 6 n: they refuse this handle from now on, so it goes
+    if (h->rel.arena) { hipFree(h->rel.arena); for (hipEvent_t e : h->rel.ev) if (e) hipEventDestroy(e); h->rel = SchurRel{}; }
+    if (h->q.arena) { hipFree(h->q.arena); for (hipEvent_t e : h->q.ev) if (e) hipEventDestroy(e); h->q = SchurQuery{}; }
+    D.arena = A; D.sigma = sigma_dyn; D.npart = npart;
+    D.steps = (int*)(A + o_st); D.r = (double*)(A + o_r); D.A = (double*)(A + o_A); D.ecost = (double*)(A + o_ec); D.part = (double*)(A + o_part);
+    D.h_part.assign(npart, 0.0);
+    // (the 6 n arrays of vba_schur_create stay in the handle's arena, unused: one allocation, freed with the handle)
+    V.N = N; V.nb = nb; V.Npad = Npad;
+    V.S = (double*)(A + o_S); V.g = (double*)(A + o_g); V.ybuf = (double*)(A + o_y); V.invL = (double*)(A + o_iL);
+    h->bw = nb - 1;             // velocity rows reach every pose column: the substitutions cover every tile of the factor
+    D.enabled = true;
+    return VBA_OK;
+}
+
 int vba_schur_last_info(vba_schur_handle h, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
     *info = h->last_info;
@@ -1901,16 +1995,29 @@ int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, flo
 }
 
 // what: 0 = step of the last iteration [6 n + 3 L] (dc then dl), 1 = lower triangle of the Cholesky factor as a dense
-// [6n][6n] row-major matrix (upper part zero), 2 = the 2 m keys |r| of the last re-weighting
+// [N][N] row-major matrix (upper part zero; N = 6 n, or 9 n with the dynamics factor), 2 = the 2 m keys |r| of the last
+// re-weighting; with the dynamics factor 3 = dv [n][3] of the last iteration, 4 = r [n - 1][6], 5 = D Phi [n - 1][6][6] and
+// 6 = sigma_dyn |r_e|^2 [n - 1] of its build
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity) {
     if (!h || !out) return sfail(VBA_EINVAL, "null argument");
     SCHK(hipSetDevice(h->device));
     SCHK(hipStreamSynchronize(h->stream));
     const SchurView& V = h->V;
     if (what == 0) {
-        if (capacity < (int64_t)V.N + 3 * (int64_t)V.L) return sfail(VBA_EINVAL, "buffer too small");
-        SCHK(hipMemcpy(out, V.g, (size_t)V.N * 8, hipMemcpyDeviceToHost));
-        SCHK(hipMemcpy(out + V.N, V.dl, (size_t)V.L * 24, hipMemcpyDeviceToHost));
+        const int64_t n6 = 6 * (int64_t)V.n;      // (the pose unknowns come first, with or without the velocities behind them)
+        if (capacity < n6 + 3 * (int64_t)V.L) return sfail(VBA_EINVAL, "buffer too small");
+        SCHK(hipMemcpy(out, V.g, (size_t)n6 * 8, hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(out + n6, V.dl, (size_t)V.L * 24, hipMemcpyDeviceToHost));
+        return VBA_OK;
+    }
+    if (what >= 3 && what <= 6) {
+        const SchurDyn& D = h->dyn;
+        if (!D.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
+        const int64_t n = V.n;
+        const double* src[4] = {V.g + 6 * n, D.r, D.A, D.ecost};
+        const int64_t count[4] = {3 * n, 6 * (n - 1), 36 * (n - 1), n - 1};
+        if (capacity < count[what - 3]) return sfail(VBA_EINVAL, "buffer too small");
+        SCHK(hipMemcpy(out, src[what - 3], (size_t)count[what - 3] * 8, hipMemcpyDeviceToHost));
         return VBA_OK;
     }
     if (what == 1) {

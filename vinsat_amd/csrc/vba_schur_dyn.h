@@ -1,0 +1,35 @@
+// vba_schur_dyn.h -- what vba_schur.hip (the handle, the entry points) and vba_schur_dyn.hip (the kernels of the orbit-dynamics
+// factor of the free-landmark mode) share: the arrays of the factor and the launchers.  Internal.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace vba {
+
+struct SchurDynView {
+    int n, Npad;
+    double sigma;                   // sigma_dyn
+    double lamda;                   // damping of the trial (velocity diagonal)
+    const int* steps;               // [n - 1] one-second steps of edge i -> i + 1, each in 1 .. kSchurDynMaxGap (checked on the host)
+    double* r;                      // [n - 1][6] residual of the last build
+    double* A;                      // [n - 1][36] D Phi of the last build, row major
+    double* ecost;                  // [n - 1] sigma |r_e|^2 of the last build
+    double* part;                   // [npart] block partials of the dynamics cost, one per 256 edges
+    int npart;
+    double* S;                      // [Npad][Npad] the reduced system (lower triangle), N = 9 n
+    double* g;                      // [Npad] right-hand side, then the step: [6 n of the poses | 3 n of the velocities]
+};
+
+inline int schur_dyn_partials(int n) { return (n - 1 + 255) / 256; }
+
+// r, A, ecost at `states` [n][10]: six lanes per edge, one tangent column each
+void schur_dyn_edges_launch(const SchurDynView& W, const double* states, hipStream_t s);
+// the factor's blocks into S and g, after the reprojection kernels on the same stream; no atomics, fixed order
+void schur_dyn_scatter_launch(const SchurDynView& W, hipStream_t s);
+// the velocity columns of states_new = those of states + dv (after k_lm_update, which leaves them as they were)
+void schur_dyn_update_launch(const SchurDynView& W, const double* states, double* states_new, hipStream_t s);
+// part[b] = sum over the edges of block b of sigma |r_e|^2 at `states` (residual-only propagation), fixed order
+void schur_dyn_cost_launch(const SchurDynView& W, const double* states, hipStream_t s);
+
+}  // namespace vba

@@ -1,0 +1,94 @@
+// vba_schur_dyn.hip -- the orbit-dynamics factor of the free-landmark mode (vba_schur_enable_dynamics; ADD-ON, PARITY UNPINNED as
+// the rest of vba_schur.hip).  Model, unknown order and the scatter's work items: vba_schur_dyn_math.h.  The attitude factor stays
+// out (its Newton blocks are not symmetric; this mode's solver is a Cholesky).
+//
+// Kernels (no float atomics; every sum in a fixed order, so two runs and two handles leave the same bits):
+//   k_sdyn_edges    eight lanes per edge, six of them at work: lane c propagates the edge's start state with the tangent e_c
+//                   (rk4_step<true>, the closed-form acceleration derivative of vba_math.h) and writes column c of D Phi; lane 0 also
+//                   writes r and sigma |r|^2.  One tangent per lane as dynamics_block (vba_dyn_body.h) and not six tangents in one
+//                   thread: the six-tangent step keeps 6 x 18 doubles of tangent state live on top of the trajectory, which is the
+//                   register budget k_dynamics_pair already strains; the edges are few (n - 1) and the kernel is a latency chain of
+//                   at most 64 steps either way.
+//   k_sdyn_scatter  block per pose, thread per target entry (kSchurDynItems of them): edge i - 1's share, then edge i's
+//   k_sdyn_update   thread per pose: v_new = v + dv
+//   k_sdyn_cost     thread per edge: residual-only propagation at the given states, block partials
+#include <hip/hip_runtime.h>
+
+#include "vba_schur_dyn.h"
+#include "vba_schur_dyn_math.h"
+
+namespace vba {
+
+namespace {
+
+constexpr int kLanes = 8;           // lanes per edge (six columns; a power of two keeps an edge inside one wavefront)
+
+__global__ __launch_bounds__(256) void k_sdyn_edges(SchurDynView W, const double* states) {
+    const int gid = blockIdx.x * 256 + threadIdx.x;
+    const int e = gid / kLanes, c = gid % kLanes;
+    if (e >= W.n - 1 || c >= 6) return;
+    const double* st = states + (size_t)e * 10;
+    double xhat[6], col[6];
+    schur_dyn_edge_column(st, W.steps[e], c, xhat, col);
+    double* A = W.A + (size_t)e * 36;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) A[6 * r + c] = col[r];
+    if (c == 0) {
+        double r6[6];
+        const double s = schur_dyn_residual(xhat, st + 10, r6);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) W.r[(size_t)e * 6 + r] = r6[r];
+        W.ecost[e] = W.sigma * s;
+    }
+}
+
+__global__ __launch_bounds__(128) void k_sdyn_scatter(SchurDynView W) {
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (i >= W.n || t >= kSchurDynItems) return;
+    schur_dyn_scatter_item(W.n, W.Npad, i, t, W.sigma, W.lamda, W.A, W.r, W.S, W.g);
+}
+
+__global__ __launch_bounds__(256) void k_sdyn_update(SchurDynView W, const double* states, double* states_new) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= W.n) return;
+    const double* dv = W.g + (size_t)6 * W.n + 3 * i;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) states_new[(size_t)i * 10 + 7 + a] = states[(size_t)i * 10 + 7 + a] + dv[a];
+}
+
+__global__ __launch_bounds__(256) void k_sdyn_cost(SchurDynView W, const double* states) {
+    __shared__ double red[4];
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    double s = 0.0;
+    if (e < W.n - 1) {
+        const double* st = states + (size_t)e * 10;
+        double xhat[6], r6[6];
+        schur_dyn_predict(st, W.steps[e], xhat);
+        s = W.sigma * schur_dyn_residual(xhat, st + 10, r6);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) W.part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+}  // namespace
+
+void schur_dyn_edges_launch(const SchurDynView& W, const double* states, hipStream_t s) {
+    hipLaunchKernelGGL(k_sdyn_edges, dim3(((W.n - 1) * kLanes + 255) / 256), dim3(256), 0, s, W, states);
+}
+
+void schur_dyn_scatter_launch(const SchurDynView& W, hipStream_t s) {
+    hipLaunchKernelGGL(k_sdyn_scatter, dim3(W.n), dim3(128), 0, s, W);
+}
+
+void schur_dyn_update_launch(const SchurDynView& W, const double* states, double* states_new, hipStream_t s) {
+    hipLaunchKernelGGL(k_sdyn_update, dim3((W.n + 255) / 256), dim3(256), 0, s, W, states, states_new);
+}
+
+void schur_dyn_cost_launch(const SchurDynView& W, const double* states, hipStream_t s) {
+    hipLaunchKernelGGL(k_sdyn_cost, dim3(W.npart), dim3(256), 0, s, W, states);
+}
+
+}  // namespace vba

@@ -5,7 +5,9 @@ marginalise and no counterpart of this module in it.  This is the variant BASELI
 reference's reprojection model: the landmarks become unknowns (3 each, held by a catalogue prior ``N(X0, sigma^2 I)``), the
 landmark blocks are eliminated (3x3 inversions), and the dense reduced camera system is factorised on the matrix cores
 (``vinsat_amd/csrc/vba_schur.hip``).  It is validated against ``oracle/schur_oracle.py`` -- this repository's own CPU
-restatement -- only, and it never runs inside :func:`vinsat_amd.ba.BA`.
+restatement -- only, and it never runs inside :func:`vinsat_amd.ba.BA`.  Opt-in per handle (``time_idx=``, ``sigma_dyn=``) the
+reference's J2 orbit factor ties consecutive poses and the velocities become unknowns (``vinsat_amd/csrc/vba_schur_dyn.hip``,
+DESIGN 9.5); the attitude factor is not part of it.
 
 Host side (this file): the static structure of a window -- rows sorted by landmark, the rows of each pose, and for every
 6x6 block of the reduced system the list of row pairs that share a landmark -- is built once with NumPy and uploaded.
@@ -98,7 +100,13 @@ def build_structure(pose_of_row, landmark_of_row, n, L):
 class SchurBA:
     """Device-resident free-landmark BA problem: ``n`` poses, ``L`` landmarks, ``m`` observation rows."""
 
-    def __init__(self, states, landmarks0, uv, weights, pose_of_row, landmark_of_row, intrinsics, sigma_prior=0.05, device=0):
+    def __init__(self, states, landmarks0, uv, weights, pose_of_row, landmark_of_row, intrinsics, sigma_prior=0.05, device=0,
+                 time_idx=None, sigma_dyn=None):
+        """``time_idx [n]`` (the second of every pose) and ``sigma_dyn`` together switch on the orbit-dynamics factor with the
+        velocities as unknowns (``vba_schur_enable_dynamics`` in ``include/vinsat_ba.h``: gaps of 1 .. 64 s, no attitude
+        factor); with neither the handle is the purely visual bundle adjustment."""
+        if (time_idx is None) != (sigma_dyn is None):
+            raise ValueError("time_idx and sigma_dyn switch on the dynamics factor together: give both or neither")
         self.lib = _lib.load()
         states = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10)
         X0 = np.ascontiguousarray(landmarks0, dtype=np.float64).reshape(-1, 3)
@@ -118,6 +126,16 @@ class SchurBA:
         self._check(self.lib.vba_schur_upload(self.h, p(s["lm_ptr"]), p(s["row_pose"]), p(s["row_lm"]), p(u), p(v), p(w), p(s["pose_ptr"]),
                                               p(s["pose_rows"]), p(s["blk_i"]), p(s["blk_j"]), p(s["blk_ptr"]), p(s["pair_k"]), p(s["pair_k2"]),
                                               p(K), p(X0), float(sigma_prior)))
+        self.dynamics = time_idx is not None
+        if self.dynamics:
+            t = np.ascontiguousarray(time_idx, dtype=np.int32).reshape(-1)
+            try:
+                if t.size != self.n:
+                    raise ValueError("time_idx needs one entry per pose")
+                self._check(self.lib.vba_schur_enable_dynamics(self.h, t.ctypes.data_as(ctypes.POINTER(c_int)), float(sigma_dyn)))
+            except Exception:
+                self.close()
+                raise
         self.set_state(states, X0)
 
     def _check(self, rc):
@@ -169,8 +187,32 @@ class SchurBA:
         self._check(self.lib.vba_schur_debug_fetch(self.h, 0, out.ctypes.data_as(PD), out.size))
         return out[: 6 * self.n].reshape(self.n, 6), out[6 * self.n:].reshape(self.L, 3)
 
+    def _dynamics_fetch(self, what, shape):
+        out = np.empty(shape)
+        self._check(self.lib.vba_schur_debug_fetch(self.h, what, out.ctypes.data_as(PD), out.size))
+        return out
+
+    def last_velocity_step(self):
+        """``dv [n,3]`` of the last iterate (a handle with the dynamics factor)."""
+        return self._dynamics_fetch(3, (self.n, 3))
+
+    def dynamics_residual(self):
+        """``r [n-1,6]`` of the edges at the state the last iterate started from (a handle with the dynamics factor)."""
+        return self._dynamics_fetch(4, (self.n - 1, 6))
+
+    def dynamics_jacobian(self):
+        """``D Phi [n-1,6,6]`` of the edges at the state the last iterate started from (a handle with the dynamics factor)."""
+        return self._dynamics_fetch(5, (self.n - 1, 6, 6))
+
+    def dynamics_edge_cost(self):
+        """``sigma_dyn |r|^2 [n-1]``: the edges' shares of the cost at the state the last iterate started from."""
+        return self._dynamics_fetch(6, (self.n - 1,))
+
     def cholesky_factor(self):
-        out = np.empty((6 * self.n, 6 * self.n))
+        """The factor of the last iterate, dense lower triangular: ``[6n, 6n]``, or ``[9n, 9n]`` over ``[pose | velocity]``
+        unknowns on a handle with the dynamics factor."""
+        N = (9 if self.dynamics else 6) * self.n
+        out = np.empty((N, N))
         self._check(self.lib.vba_schur_debug_fetch(self.h, 1, out.ctypes.data_as(PD), out.size))
         return out
 

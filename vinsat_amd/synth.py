@@ -163,7 +163,7 @@ def make_subwindow(cfg: WindowConfig | str, n_poses: int, **kw):
     return det[det[:, 0] < t_end].copy(), orbit[: t_end + 5].copy()
 
 
-def make_tracked_landmarks(n_poses=40, n_landmarks=600, stride=5, seed=0, pixel_noise=1.0, catalogue_sigma_km=0.05, t0=10):
+def make_tracked_landmarks(n_poses=40, n_landmarks=600, stride=5, seed=0, pixel_noise=1.0, catalogue_sigma_km=0.05, t0=10, times=None):
     """Synthetic free-landmark problem (the add-on of ``vinsat_amd/schur.py``; the reference has no such data): ground
     landmarks scattered along the ground track, each seen from every frame whose footprint (+-1.2 deg latitude, +-2 deg
     longitude around the sub-satellite point, as :func:`make_sequence`) contains it -- tracks of several frames.
@@ -172,12 +172,20 @@ def make_tracked_landmarks(n_poses=40, n_landmarks=600, stride=5, seed=0, pixel_
     taken at the Earth rotation angle of the first frame that sees it: the add-on treats landmarks as inertial points, so
     frames are kept within ~1 minute where the ground moves less than the catalogue uncertainty would allow -- synthetic
     data for the solver, not a model of the real scene), ``X0`` = truth + catalogue error, ``uv``, ``pose_of_row``,
-    ``landmark_of_row``, ``intrinsics [n,4]``.
+    ``landmark_of_row``, ``intrinsics [n,4]``.  ``times`` (increasing seconds, one per pose) replaces the even spacing
+    ``t0 + stride * i``; the dict then carries them as ``time_idx``.
     """
     rng = np.random.default_rng(seed)
-    n_sec = t0 + n_poses * stride + 5
+    if times is None:
+        n_sec = t0 + n_poses * stride + 5
+        times = t0 + stride * np.arange(n_poses)
+        extra = {}
+    else:
+        times = np.asarray(times, dtype=np.int64).reshape(-1)
+        n_poses = times.size
+        n_sec = int(times[-1]) + 6
+        extra = dict(time_idx=times.copy())
     traj = integrate_orbit(n_sec)
-    times = t0 + stride * np.arange(n_poses)
     pos = traj[times, :3]
     vel = traj[times, 3:]
     quat = frames.nadir_quaternion(pos)
@@ -215,7 +223,7 @@ def make_tracked_landmarks(n_poses=40, n_landmarks=600, stride=5, seed=0, pixel_
     landmark_of_row = remap[landmark_of_row]
     X0 = X + rng.normal(0.0, catalogue_sigma_km, X.shape)
     return dict(states_gt=states, X_true=X, X0=X0, uv=uv, pose_of_row=pose_of_row, landmark_of_row=landmark_of_row,
-                intrinsics=np.repeat(INTRINSICS[None], n_poses, 0), sigma=catalogue_sigma_km)
+                intrinsics=np.repeat(INTRINSICS[None], n_poses, 0), sigma=catalogue_sigma_km, **extra)
 
 
 def make_two_pass_sequence(n_poses=12, obs_per_pose=6, stride=5, gap=1500, seed=4, pixel_noise=1.0, conf=0.95, tail=140):
