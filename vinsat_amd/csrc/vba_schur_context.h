@@ -1,0 +1,262 @@
+// vba_schur_context.h -- the host side of the free-landmark mode shared by its translation units (the map of the units and of
+// their kernels heads vba_schur.hip): the view the kernels take, the row geometry three units reproject with, the context behind a
+// vba_schur_handle with the state of every feature, error reporting, the scratch helper behind the features, and the functions one
+// unit defines and another calls.  Internal.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/vinsat_ba.h"
+#include "vba_math.h"
+#include "vba_schur_dyn.h"
+
+using namespace vba;
+
+// (everything below is internal to the library: hidden, as vba_context.h is)
+#pragma GCC visibility push(hidden)
+
+typedef double vf4 __attribute__((ext_vector_type(4)));
+
+constexpr int kT = 64;              // tile of the blocked Cholesky
+constexpr int kPanel = 4;           // tile columns per panel: the trailing update runs with K = kPanel * kT = 256 (round 4)
+
+struct SchurView {
+    int n, L;
+    int64_t m;
+    int N, Npad, nb;                // reduced system: N = 6 n (9 n with the dynamics factor), padded to a multiple of kT, nb tiles per side
+    // rows sorted by landmark: CSR lm_ptr[L+1]
+    const int* lm_ptr;
+    const int* row_pose;            // [m]
+    const int* row_lm;              // [m]
+    const double *row_u, *row_v, *row_w;    // [m] measurement, weight
+    // rows of a pose: CSR pose_ptr[n+1] -> pose_rows[m] (indices into the landmark-sorted rows)
+    const int* pose_ptr;
+    const int* pose_rows;
+    // blocks (i >= j) of S that receive pair products: CSR blk_ptr[nblk+1] -> (pair_k, pair_k2); blk_i, blk_j
+    int nblk;
+    const int *blk_i, *blk_j, *blk_ptr, *pair_k, *pair_k2;
+    const double* intr;             // [n][4]
+    const double* X0;               // [L][3] catalogue positions
+    double inv_sigma2;              // 1 / sigma_prior^2
+    double lamda;
+    // state
+    const double* states;           // [n][10]
+    const double* X;                // [L][3]
+    double* states_new;
+    double* X_new;
+    // work
+    double* Cinv;                   // [L][6] symmetric inverse (00,01,02,11,12,22)
+    double* wl;                     // [L][3]
+    double* E;                      // [m][18] row major 6x3
+    double* Y;                      // [m][18]
+    double* S;                      // [Npad][Npad] row major, lower triangle used
+    double* g;                      // [Npad] right-hand side, then the step of the poses
+    double* ybuf;                   // [Npad] intermediate of the two substitutions
+    double* invL;                   // [nb][kT*kT] inverse of the diagonal Cholesky factors
+    double* dl;                     // [L][3]
+    double* part;                   // cost partials
+    int npart;
+};
+
+// The reduced system of N unknowns in whole panels of tiles (the padding rows are an identity block): nb tiles per side, Npad rows
+inline void schur_padded_size(int N, int& nb, int& Npad) {
+    nb = (N + kT * kPanel - 1) / (kT * kPanel) * kPanel;
+    Npad = nb * kT;
+}
+
+// row k of the landmark-sorted rows: residual, A (d uv / d p_c), camera point, for pose / landmark state given
+struct RowGeom {
+    double ru, rv, a00, a02, a11, a12, cam[3];
+    PoseCam pc;
+};
+
+__device__ __forceinline__ void row_geometry(const SchurView& V, const double* states, const double* X, int k, RowGeom& q) {
+    const int i = V.row_pose[k], l = V.row_lm[k];
+    pose_camera(states + (size_t)i * 10, V.intr + (size_t)i * 4, q.pc);
+    double u, v, d;
+    project(q.pc, X[3 * l], X[3 * l + 1], X[3 * l + 2], u, v, q.cam, d);
+    q.ru = V.row_u[k] - u;
+    q.rv = V.row_v[k] - v;
+    const double live = q.cam[2] > kZMin ? 1.0 : 0.0;
+    q.a00 = q.pc.fx * d;
+    q.a11 = q.pc.fy * d;
+    q.a02 = -(q.a00 * (q.cam[0] * d * live));
+    q.a12 = -(q.a11 * (q.cam[1] * d * live));
+}
+
+// J_l = A R^T (2x3): row u -> jl[0..2], row v -> jl[3..5]
+__device__ __forceinline__ void landmark_jacobian(const RowGeom& q, double* jl) {
+    const double* R = q.pc.R;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        jl[c] = q.a00 * R[3 * c] + q.a02 * R[3 * c + 2];
+        jl[3 + c] = q.a11 * R[3 * c + 1] + q.a12 * R[3 * c + 2];
+    }
+}
+
+// J_c = [-J_l | 2 A hat(p_c)] (2x6): row u -> jc[0..5], row v -> jc[6..11]
+__device__ __forceinline__ void pose_jacobian(const RowGeom& q, const double* jl, double* jc) {
+    const double x = q.cam[0], y = q.cam[1], z = q.cam[2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { jc[c] = -jl[c]; jc[6 + c] = -jl[3 + c]; }
+    jc[3] = 2.0 * (-q.a02 * y);
+    jc[4] = 2.0 * (-q.a00 * z + q.a02 * x);
+    jc[5] = 2.0 * (q.a00 * y);
+    jc[9] = 2.0 * (q.a11 * z - q.a12 * y);
+    jc[10] = 2.0 * (q.a12 * x);
+    jc[11] = 2.0 * (-q.a11 * x);
+}
+
+// ---- error reporting (vba_schur.hip holds the thread-local text that vba_schur_last_error returns)
+int sfail(int code, const std::string& msg);
+#define SCHK(expr)                                                                                     \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) return sfail(VBA_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// ---- scratch of a feature (vba_schur.hip)
+// The arrays of one allocation, one after the other, each on a 256-byte boundary: need(b) is the offset of the next one.
+struct SchurLayout {
+    size_t bytes = 0;
+    size_t need(size_t b) { const size_t o = bytes; bytes += (b + 255) & ~size_t(255); return o; }
+};
+
+// What every feature allocates on its first call: one zeroed arena, the two events around its timed section, the last reading.
+struct SchurScratch {
+    char* arena = nullptr;
+    hipEvent_t ev[2] = {};
+    float ms = 0.0f;
+};
+// arena (zeroed) and events, or nothing at all; `what` names the scratch in the message of a failure
+int schur_scratch_alloc(SchurScratch& Z, size_t bytes, const char* what);
+// events and arena go, Z is as it was before its allocation
+void schur_scratch_release(SchurScratch& Z);
+// End of the timed section on stream s: ev[1], then whatever `copies` enqueues behind it (the copies to the host stay outside the
+// reported milliseconds), the wait for the stream, ms = ev[0] .. ev[1].
+template <class Copies>
+int schur_scratch_finish(SchurScratch& Z, hipStream_t s, Copies copies) {
+    SCHK(hipEventRecord(Z.ev[1], s));
+    if (int rc = copies()) return rc;
+    SCHK(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&Z.ms, Z.ev[0], Z.ev[1]);
+    return VBA_OK;
+}
+inline int schur_scratch_finish(SchurScratch& Z, hipStream_t s) { return schur_scratch_finish(Z, s, [] { return (int)VBA_OK; }); }
+
+// ---- state of the features
+// Scratch of vba_schur_covariance, allocated by the first query of a handle: every array the build and the factorisation write,
+// W, the gathered blocks and the landmarks' pair -> block index (built on the host from the uploaded lists, once per upload).
+struct SchurQuery {
+    SchurScratch sc;
+    double *Cinv = nullptr, *wl = nullptr, *E = nullptr, *Y = nullptr, *S = nullptr, *g = nullptr, *ybuf = nullptr, *invL = nullptr, *dl = nullptr;
+    double *W = nullptr, *pair = nullptr, *pose = nullptr, *lm = nullptr;
+    int *info = nullptr, *lp_ptr = nullptr, *lp_blk = nullptr;
+    bool indexed = false;
+};
+
+// What vba_schur_reliability needs beyond that, allocated by the first reliability query of a handle: its outputs on the device,
+// the per-row and per-landmark cost terms of the totals, and two timing events of its own.
+struct SchurRel {
+    SchurScratch sc;
+    double *lev = nullptr, *wt = nullptr, *om = nullptr, *lmlev = nullptr, *lmwt = nullptr, *lmom = nullptr, *lm_stats = nullptr,
+           *pose_stats = nullptr, *fit = nullptr;
+};
+
+// State of vba_schur_snoop, allocated by the first snoop of a handle and cleared by vba_schur_upload: the weight a rejected row
+// had and a byte per row, a byte per landmark (both cumulative), the per-call decisions of the passes, two timing events.
+struct SchurSnoop {
+    SchurScratch sc;
+    double *saved = nullptr, *crit_used = nullptr;
+    unsigned char *row_mask = nullptr, *lm_mask = nullptr;
+    int *lm_dec = nullptr, *pose_pick = nullptr, *pose_short = nullptr, *pose_out = nullptr, *lm_out = nullptr;
+    int totals[3] = {0, 0, 0};  // rows rejected by their own test, landmarks rejected, rows zeroed through rejected landmarks
+};
+
+// State of vba_schur_reweight, allocated by the first re-weighting of a handle and cleared by vba_schur_upload: the weights as
+// uploaded, the 2 m keys |r| and the raw weights of the last call, the select's histograms, two timing events.
+struct SchurRobust {
+    SchurScratch sc;
+    double *base = nullptr, *keys = nullptr, *q = nullptr, *part = nullptr, *res = nullptr;
+    unsigned long long *hist = nullptr, *state = nullptr;
+    bool captured = false;      // base holds the weights of the current upload
+    bool have_keys = false;     // keys are those of a re-weighting since the current upload
+    int launches = 0;           // kernel launches of the last re-weighting
+};
+
+// State of vba_schur_enable_dynamics: the reduced system re-sized for N = 9 n (S, g, ybuf, invL: the view points here from then on),
+// the edges' step counts, the factor of the last build and the partials of its cost.
+struct SchurDyn {
+    char* arena = nullptr;
+    bool enabled = false;
+    double sigma = 0.0;
+    int* steps = nullptr;
+    double *r = nullptr, *A = nullptr, *ecost = nullptr, *part = nullptr;
+    int npart = 0;
+    std::vector<double> h_part;
+};
+
+// why the three queries refuse a handle with the dynamics factor
+constexpr char kDynRefusal[] = " is not available on a handle with the dynamics factor: its redundancy counts and gathers assume the "
+                               "6 n reduced system of the reprojection rows";
+
+struct vba_schur_context {
+    int device = 0;
+    SchurView V{};
+    char* arena = nullptr;
+    hipStream_t stream = nullptr, aux = nullptr;    // aux: the bulk of a panel's trailing update beside the next panel's factorisation
+    hipEvent_t ev[5] = {};
+    hipEvent_t ev_chain = nullptr, ev_bulk = nullptr;
+    int classic = 0;                // VBA_SCHUR_CLASSIC=1: the round-2 tile-by-tile factorisation (comparison)
+    int* d_info = nullptr;
+    int last_info = 0;              // 0, or 1 + the row at which the last factorisation met a non-positive pivot
+    double* S0 = nullptr;       // states buffers
+    double* S1 = nullptr;
+    double* X0buf = nullptr;
+    double* X1buf = nullptr;
+    std::vector<double> h_part;
+    bool uploaded = false, have_state = false;
+    float ms[4] = {0, 0, 0, 0};
+    int64_t npairs = 0;
+    SchurQuery q;               // vba_schur_covariance's scratch (nothing until the first query)
+    SchurRel rel;               // vba_schur_reliability's scratch on top of it (nothing until the first reliability query)
+    SchurSnoop snoop;           // vba_schur_snoop's state (nothing until the first snoop)
+    SchurRobust robust;         // vba_schur_reweight's state (nothing until the first re-weighting)
+    SchurDyn dyn;               // vba_schur_enable_dynamics' state (nothing on a handle without the dynamics factor)
+    int bw = 1 << 30;           // tile bandwidth of the reduced system (max |I - J| over its non-zero tiles), from the block list
+};
+
+// ---- vba_schur_build.hip
+// S, g, Cinv, wl, E, Y of the view's state and damping on stream s (S and g zeroed by the caller): the reprojection blocks, the
+// dynamics blocks on a handle with the factor, the identity of the padding rows
+void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s);
+
+// ---- vba_schur_factor.hip
+// S = Lg Lg^T in place and the inverse diagonal factors, on stream s (the bulk of a panel's trailing update beside it on h->aux);
+// *d_info (zeroed by the caller) keeps 1 + the first row with a non-positive pivot
+int schur_factor_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info);
+
+// ---- vba_schur.hip
+int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built);
+
+// ---- vba_schur_cov.hip
+int schur_query_alloc(vba_schur_handle h);
+int schur_query_index(vba_schur_handle h);
+int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad);
+
+// ---- vba_schur_rel.hip
+int schur_rel_alloc(vba_schur_handle h);
+int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad);
+
+// ---- vba_schur_dyn.hip
+// the dynamics arrays of a handle with the factor enabled, at the damping of the view
+SchurDynView schur_dyn_view(vba_schur_handle h, const SchurView& V);
+#pragma GCC visibility pop

@@ -1,5 +1,5 @@
-// vba_schur_dyn.h -- what vba_schur.hip (the handle, the entry points) and vba_schur_dyn.hip (the kernels of the orbit-dynamics
-// factor of the free-landmark mode) share: the arrays of the factor and the launchers.  Internal.
+// vba_schur_dyn.h -- what the units that build, step and cost a handle (vba_schur.hip, vba_schur_build.hip) and vba_schur_dyn.hip (the
+// kernels of the orbit-dynamics factor of the free-landmark mode) share: the arrays of the factor and the launchers.  Internal.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // vba_schur_dyn.hip -- the orbit-dynamics factor of the free-landmark mode (vba_schur_enable_dynamics; ADD-ON, PARITY UNPINNED as
-// the rest of vba_schur.hip).  Model, unknown order and the scatter's work items: vba_schur_dyn_math.h.  The attitude factor stays
+// the rest of the mode: vba_schur.hip carries the map of the units): its kernels, then the entry point.  Model, unknown order and the scatter's work items: vba_schur_dyn_math.h.  The attitude factor stays
 // out (its Newton blocks are not symmetric; this mode's solver is a Cholesky).
 //
 // Kernels (no float atomics; every sum in a fixed order, so two runs and two handles leave the same bits):
@@ -14,6 +14,7 @@
 //   k_sdyn_cost     thread per edge: residual-only propagation at the given states, block partials
 #include <hip/hip_runtime.h>
 
+#include "vba_schur_context.h"
 #include "vba_schur_dyn.h"
 #include "vba_schur_dyn_math.h"
 
@@ -92,3 +93,65 @@ void schur_dyn_cost_launch(const SchurDynView& W, const double* states, hipStrea
 }
 
 }  // namespace vba
+
+SchurDynView schur_dyn_view(vba_schur_handle h, const SchurView& V) {
+    const SchurDyn& D = h->dyn;
+    SchurDynView W{};
+    W.n = V.n; W.Npad = V.Npad; W.sigma = D.sigma; W.lamda = V.lamda;
+    W.steps = D.steps; W.r = D.r; W.A = D.A; W.ecost = D.ecost; W.part = D.part; W.npart = D.npart;
+    W.S = V.S; W.g = V.g;
+    return W;
+}
+
+extern "C" int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx, double sigma_dyn) {
+    if (!h || !time_idx) return sfail(VBA_EINVAL, "null argument");
+    if (!h->uploaded) return sfail(VBA_ESTATE, "upload the problem first");
+    if (h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is already enabled on this handle");
+    if (!(sigma_dyn > 0.0) || !std::isfinite(sigma_dyn)) return sfail(VBA_EINVAL, "sigma_dyn must be positive and finite");
+    SchurView& V = h->V;
+    const int n = V.n;
+    if (n < 2) return sfail(VBA_EINVAL, "the dynamics factor needs at least two poses");
+    std::vector<int> steps(n - 1);
+    for (int i = 0; i + 1 < n; ++i) {
+        const int64_t d = (int64_t)time_idx[i + 1] - (int64_t)time_idx[i];
+        if (d < 1) return sfail(VBA_EINVAL, "time_idx must increase: poses " + std::to_string(i) + " and " + std::to_string(i + 1));
+        if (d > kSchurDynMaxGap)
+            return sfail(VBA_EINVAL, "a gap of " + std::to_string(d) + " steps between poses " + std::to_string(i) + " and " + std::to_string(i + 1) +
+                                         ": the dynamics factor of this mode covers gaps of 1 .. " + std::to_string(kSchurDynMaxGap) + " steps");
+        steps[i] = (int)d;
+    }
+    SCHK(hipSetDevice(h->device));
+    SCHK(hipStreamSynchronize(h->stream));
+    const int N = 9 * n;
+    int nb, Npad;
+    schur_padded_size(N, nb, Npad);
+    SchurDyn& D = h->dyn;
+    const int npart = schur_dyn_partials(n);
+    SchurLayout lay;
+    const size_t o_S = lay.need((size_t)Npad * Npad * 8), o_g = lay.need((size_t)Npad * 8), o_y = lay.need((size_t)Npad * 8),
+                 o_iL = lay.need((size_t)nb * kT * kT * 8);
+    const size_t o_st = lay.need((size_t)(n - 1) * 4), o_r = lay.need((size_t)(n - 1) * 48), o_A = lay.need((size_t)(n - 1) * 288),
+                 o_ec = lay.need((size_t)(n - 1) * 8), o_part = lay.need((size_t)npart * 8);
+    const size_t bytes = lay.bytes;
+    char* A = nullptr;
+    if (hipMalloc(&A, bytes) != hipSuccess) { (void)hipGetLastError(); return sfail(VBA_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes for the dynamics factor failed"); }
+    if (hipMemset(A, 0, bytes) != hipSuccess || hipMemcpy(A + o_st, steps.data(), (size_t)(n - 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {
+        hipFree(A);
+        return sfail(VBA_EHIP, "dynamics factor: hipMemset / upload failed");
+    }
+    // the scratch of the queries was sized for 6 n: they refuse this handle from now on, so it goes
+    schur_scratch_release(h->rel.sc);
+    h->rel = SchurRel{};
+    schur_scratch_release(h->q.sc);
+    h->q = SchurQuery{};
+    D.arena = A; D.sigma = sigma_dyn; D.npart = npart;
+    D.steps = (int*)(A + o_st); D.r = (double*)(A + o_r); D.A = (double*)(A + o_A); D.ecost = (double*)(A + o_ec); D.part = (double*)(A + o_part);
+    D.h_part.assign(npart, 0.0);
+    // (the 6 n arrays of vba_schur_create stay in the handle's arena, unused: one allocation, freed with the handle)
+    V.N = N; V.nb = nb; V.Npad = Npad;
+    V.S = (double*)(A + o_S); V.g = (double*)(A + o_g); V.ybuf = (double*)(A + o_y); V.invL = (double*)(A + o_iL);
+    h->bw = nb - 1;             // velocity rows reach every pose column: the substitutions cover every tile of the factor
+    D.enabled = true;
+    return VBA_OK;
+}

@@ -1,0 +1,257 @@
+// vba_schur_rel.hip -- the reliability query of the free-landmark mode (vba_schur_reliability; include/vinsat_ba.h carries the
+// contract): the device part of the covariance query (vba_schur_cov.hip), then leverage and w-test of every row and of every
+// catalogue prior, the statistics per landmark and per pose, the totals of the fit.  Its device part is what vba_schur_snoop starts
+// with.  vba_schur.hip carries the map of the units; the closed forms are vba_schur_rel_math.h.
+#include "vba_schur_context.h"
+#include "vba_schur_rel_math.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ reliability query
+// vba_schur_reliability, after the device part of the covariance query (gathered blocks, Y, Cinv, landmark marginals resident).
+//
+// Row pass, THREAD PER ROW k (pose i, landmark l, position a in the track of l):
+//   Sigma_il = -sum_{k' in rows(l)} (S^-1)_{i, pose(k')} Y_k'   (6x3, k' upwards; the block of the pair from lp_blk, which lists
+//                                                               k >= k' only: for k' > k the block of (k', k) is read transposed)
+//   P_k = w [A Al] [[Sigma_ii, Sigma_il], [Sigma_il^T, Sigma_ll]] [A Al]^T   (symmetric part), leverage = tr P_k, w-test by
+//   rel_wtest2.  A row costs t products of 6x6 by 6x3 for a track of t rows, so the rows of a landmark together cost the t^2 of
+//   k_lm_cov -- spread over t threads that sit side by side in a wave and read the same Y and the same blocks.
+// om[k] = w |r|^2 is kept for the totals.
+__global__ __launch_bounds__(256) void k_rel_rows(SchurView V, const double* pair, const int* lp_ptr, const int* lp_blk, const double* lm,
+                                                  double* lev, double* wt, double* om) {
+    const int64_t k64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k64 >= V.m) return;
+    const int k = (int)k64;
+    const double w = V.row_w[k];
+    RowGeom q;
+    row_geometry(V, V.states, V.X, k, q);
+    om[k] = w * (q.ru * q.ru + q.rv * q.rv);
+    if (w == 0.0) { lev[k] = 0.0; wt[k] = 0.0; return; }
+    const int l = V.row_lm[k], beg = V.lm_ptr[l], end = V.lm_ptr[l + 1], a = k - beg, base = lp_ptr[l];
+    double G[18];                   // sum (S^-1)_{i, pose(k')} Y_k' = -Sigma_il
+#pragma unroll
+    for (int e = 0; e < 18; ++e) G[e] = 0.0;
+    for (int k2 = beg; k2 < end; ++k2) {
+        const int c = k2 - beg;
+        const bool tr = c > a;
+        const int slot = base + (tr ? c * (c + 1) / 2 + a : a * (a + 1) / 2 + c);
+        const double* Sg = pair + (size_t)lp_blk[slot] * 36;
+        const int sp = tr ? 1 : 6, sq = tr ? 6 : 1;    // entry (p, q) of (S^-1)_{i, pose(k')}: Sg[p sp + q sq]
+        double Y2[18];
+#pragma unroll
+        for (int e = 0; e < 18; ++e) Y2[e] = V.Y[(size_t)k2 * 18 + e];
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+            double g[6];
+#pragma unroll
+            for (int qq = 0; qq < 6; ++qq) g[qq] = Sg[p * sp + qq * sq];
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) {
+                double s = G[3 * p + cc];
+#pragma unroll
+                for (int qq = 0; qq < 6; ++qq) s = fma(g[qq], Y2[3 * qq + cc], s);
+                G[3 * p + cc] = s;
+            }
+        }
+    }
+    double jl[6], jc[12];
+    landmark_jacobian(q, jl);
+    pose_jacobian(q, jl, jc);
+    // A Sigma_ii A^T from the diagonal block of the row's own pair (k, k): stored whole and exactly symmetric
+    const double* Sii = pair + (size_t)lp_blk[base + a * (a + 1) / 2 + a] * 36;
+    double q00 = 0.0, q01 = 0.0, q11 = 0.0;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+        double tu = 0.0, tv = 0.0;
+#pragma unroll
+        for (int qq = 0; qq < 6; ++qq) { tu = fma(Sii[6 * p + qq], jc[qq], tu); tv = fma(Sii[6 * p + qq], jc[6 + qq], tv); }
+        q00 = fma(jc[p], tu, q00);
+        q01 = fma(jc[p], tv, q01);
+        q11 = fma(jc[6 + p], tv, q11);
+    }
+    // A (-Sigma_il) Al^T: x = A G (2x3), then against the rows of Al
+    double x00 = 0.0, x01 = 0.0, x10 = 0.0, x11 = 0.0;
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) {
+        double xu = 0.0, xv = 0.0;
+#pragma unroll
+        for (int p = 0; p < 6; ++p) { xu = fma(jc[p], G[3 * p + cc], xu); xv = fma(jc[6 + p], G[3 * p + cc], xv); }
+        x00 = fma(xu, jl[cc], x00);
+        x01 = fma(xu, jl[3 + cc], x01);
+        x10 = fma(xv, jl[cc], x10);
+        x11 = fma(xv, jl[3 + cc], x11);
+    }
+    // Al Sigma_ll Al^T
+    const double* Sl = lm + (size_t)l * 9;
+    double l00 = 0.0, l01 = 0.0, l11 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double yu = fma(Sl[3 * r], jl[0], fma(Sl[3 * r + 1], jl[1], Sl[3 * r + 2] * jl[2]));
+        const double yv = fma(Sl[3 * r], jl[3], fma(Sl[3 * r + 1], jl[4], Sl[3 * r + 2] * jl[5]));
+        l00 = fma(jl[r], yu, l00);
+        l01 = fma(jl[r], yv, l01);
+        l11 = fma(jl[3 + r], yv, l11);
+    }
+    const double p00 = w * ((q00 + l00) - (x00 + x00));
+    const double p01 = w * ((q01 + l01) - (x01 + x10));
+    const double p11 = w * ((q11 + l11) - (x11 + x11));
+    lev[k] = p00 + p11;
+    wt[k] = rel_wtest2(p00, p01, p11, q.ru, q.rv, w);
+}
+
+// sum of leverage, largest finite w-test, count of rows with w > 0 over a list of rows in list order (idx == nullptr: beg .. end)
+__device__ __forceinline__ void rel_row_stats(const SchurView& V, const int* idx, int beg, int end, const double* lev, const double* wt, double* out) {
+    double s = 0.0, mx = 0.0, cnt = 0.0;
+    for (int r = beg; r < end; ++r) {
+        const int k = idx ? idx[r] : r;
+        s += lev[k];
+        const double t = wt[k];
+        if (t <= 1.79e308 && t > mx) mx = t;    // (NaN fails both)
+        cnt += V.row_w[k] > 0.0 ? 1.0 : 0.0;
+    }
+    out[0] = s; out[1] = mx; out[2] = cnt;
+}
+
+// Thread id < L: the statistics of landmark id over its rows and the test of its catalogue prior as an observation,
+// e = X - X0, P_l = Sigma_ll / sigma^2; lmom = |e|^2 / sigma^2 is kept for the totals.  Thread id < n: the statistics of pose id.
+__global__ __launch_bounds__(256) void k_rel_stats(SchurView V, const double* lm, const double* lev, const double* wt, double* lmlev, double* lmwt,
+                                                   double* lmom, double* lm_stats, double* pose_stats) {
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id < V.L) {
+        const int l = id, beg = V.lm_ptr[l], end = V.lm_ptr[l + 1];
+        rel_row_stats(V, nullptr, beg, end, lev, wt, lm_stats + (size_t)l * 3);
+        const double e[3] = {V.X[3 * l] - V.X0[3 * l], V.X[3 * l + 1] - V.X0[3 * l + 1], V.X[3 * l + 2] - V.X0[3 * l + 2]};
+        lmom[l] = V.inv_sigma2 * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+        if (beg == end) {           // tested by nothing: the closed form of k_lm_cov's d
+            const double d = 1.0 / (V.inv_sigma2 + V.lamda);
+            lmlev[l] = (3.0 * d) * V.inv_sigma2;
+            lmwt[l] = 0.0;
+        } else {
+            const double* Sl = lm + (size_t)l * 9;
+            const double is2 = V.inv_sigma2;
+            const double p[6] = {Sl[0] * is2, Sl[1] * is2, Sl[2] * is2, Sl[4] * is2, Sl[5] * is2, Sl[8] * is2};
+            lmlev[l] = (p[0] + p[3]) + p[5];
+            const double mI[6] = {1.0 - p[0], -p[1], -p[2], 1.0 - p[3], -p[4], 1.0 - p[5]};
+            lmwt[l] = rel_wtest3(mI, e, is2);
+        }
+    }
+    if (id < V.n) rel_row_stats(V, V.pose_rows, V.pose_ptr[id], V.pose_ptr[id + 1], lev, wt, pose_stats + (size_t)id * 3);
+}
+
+// Totals, ONE block: thread t sums the rows t, t + 256, ... and the landmarks likewise, then a tree over the 256 partials -- one
+// shape for every problem.  fit[8] = Omega, m_eff, t_rows, t_prior, rho, s0sq, largest finite row / landmark w-test.
+__global__ __launch_bounds__(256) void k_rel_totals(SchurView V, const double* lev, const double* wt, const double* om, const double* lmlev,
+                                                    const double* lmwt, const double* lmom, double* fit) {
+    __shared__ double red[7][256];
+    const int t = threadIdx.x;
+    double a[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // om rows, m_eff, t_rows, max row, om prior, t_prior, max landmark
+    for (int64_t k = t; k < V.m; k += 256) {
+        a[0] += om[k];
+        a[1] += V.row_w[k] > 0.0 ? 1.0 : 0.0;
+        a[2] += lev[k];
+        const double x = wt[k];
+        if (x <= 1.79e308 && x > a[3]) a[3] = x;
+    }
+    for (int l = t; l < V.L; l += 256) {
+        a[4] += lmom[l];
+        a[5] += lmlev[l];
+        const double x = lmwt[l];
+        if (x <= 1.79e308 && x > a[6]) a[6] = x;
+    }
+#pragma unroll
+    for (int e = 0; e < 7; ++e) red[e][t] = a[e];
+    for (int o = 128; o > 0; o >>= 1) {
+        __syncthreads();
+        if (t < o) {
+#pragma unroll
+            for (int e = 0; e < 7; ++e) {
+                const double x = red[e][t], y = red[e][t + o];
+                red[e][t] = (e == 3 || e == 6) ? (y > x ? y : x) : x + y;
+            }
+        }
+    }
+    if (t == 0) {
+        const double Omega = red[0][0] + red[4][0], meff = red[1][0], trows = red[2][0], tprior = red[5][0];
+        const double rho = ((2.0 * meff + 3.0 * (double)V.L) - trows) - tprior;
+        fit[0] = Omega; fit[1] = meff; fit[2] = trows; fit[3] = tprior; fit[4] = rho;
+        fit[5] = rho > 0.0 ? Omega / rho : __builtin_nan("");
+        fit[6] = red[3][0]; fit[7] = red[6][0];
+    }
+}
+
+}  // namespace
+
+// first reliability query of a handle: its scratch and its two timing events
+int schur_rel_alloc(vba_schur_handle h) {
+    SchurRel& R = h->rel;
+    if (R.sc.arena) return VBA_OK;
+    const SchurView& V = h->V;
+    const size_t m = (size_t)V.m, L = (size_t)V.L;
+    SchurLayout lay;
+    const size_t o_lev = lay.need(m * 8), o_wt = lay.need(m * 8), o_om = lay.need(m * 8), o_ll = lay.need(L * 8), o_lw = lay.need(L * 8),
+                 o_lo = lay.need(L * 8), o_ls = lay.need(L * 24), o_ps = lay.need((size_t)V.n * 24), o_fit = lay.need(64);
+    if (int rc = schur_scratch_alloc(R.sc, lay.bytes, "reliability scratch")) return rc;
+    char* A = R.sc.arena;
+    R.lev = (double*)(A + o_lev); R.wt = (double*)(A + o_wt); R.om = (double*)(A + o_om); R.lmlev = (double*)(A + o_ll); R.lmwt = (double*)(A + o_lw);
+    R.lmom = (double*)(A + o_lo); R.lm_stats = (double*)(A + o_ls); R.pose_stats = (double*)(A + o_ps); R.fit = (double*)(A + o_fit);
+    return VBA_OK;
+}
+
+// The device part of vba_schur_reliability, shared with vba_schur_snoop: schur_query_device with the landmark marginals from
+// ev_begin on, and unless the factorisation failed (*bad != 0: nothing more is launched) the three passes into the reliability
+// scratch.  The launches and their order are those vba_schur_reliability has always issued.
+int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad) {
+    SchurQuery& Q = h->q;
+    SchurRel& R = h->rel;
+    hipStream_t s = h->stream;
+    if (int rc = schur_query_device(h, lamda, true, ev_begin, V, bad)) return rc;
+    if (*bad != 0) return VBA_OK;
+    // every output is formed whatever is asked for: what is asked for decides the copies only
+    hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
+    hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
+                       R.pose_stats);
+    hipLaunchKernelGGL(k_rel_totals, dim3(1), dim3(256), 0, s, V, R.lev, R.wt, R.om, R.lmlev, R.lmwt, R.lmom, R.fit);
+    return VBA_OK;
+}
+
+extern "C" {
+
+int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
+                          double* lm_stats, double* pose_stats, double* fit, int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_reliability") + kDynRefusal);
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    if (int rc = schur_query_index(h)) return rc;
+    if (int rc = schur_rel_alloc(h)) return rc;
+    SchurRel& R = h->rel;
+    hipStream_t s = h->stream;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_rel_device(h, lamda, R.sc.ev[0], V, &bad)) return rc;
+    *info = bad;
+    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
+    struct Out { double* host; const double* dev; size_t count; };
+    const Out outs[7] = {{leverage, R.lev, m}, {wtest, R.wt, m}, {lm_leverage, R.lmlev, L}, {lm_wtest, R.lmwt, L}, {lm_stats, R.lm_stats, 3 * L},
+                         {pose_stats, R.pose_stats, 3 * n}, {fit, R.fit, 8}};
+    if (bad != 0) {                 // no factor, no covariance, no test: NaN, and the row in *info
+        if (int rc = schur_scratch_finish(R.sc, s)) return rc;
+        for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
+        return VBA_OK;
+    }
+    return schur_scratch_finish(R.sc, s, [&]() -> int {
+        SCHK(hipGetLastError());
+        for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
+        return VBA_OK;
+    });
+}
+
+int vba_schur_last_reliability_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->rel.sc.ms;
+    return VBA_OK;
+}
+
+}  // extern "C"

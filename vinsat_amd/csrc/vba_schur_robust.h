@@ -1,5 +1,5 @@
-// vba_schur_robust.h -- what vba_schur.hip (the handle, the entry points) and vba_schur_robust.hip (the passes) share: the arrays
-// the passes of vba_schur_reweight read and write, the exact radix select that vba_schur_median runs on its own, and their
+// vba_schur_robust.h -- what the entry points of vba_schur_robust.hip fill from the handle (vba_schur_context.h) and its kernels take
+// by value: the arrays the passes of vba_schur_reweight read and write, the exact radix select that vba_schur_median runs on its own, and their
 // launchers.  Internal.
 #pragma once
 

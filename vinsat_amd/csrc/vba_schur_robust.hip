@@ -1,8 +1,8 @@
-// vba_schur_robust.hip -- the passes of the free-landmark fit's robust re-weighting (vba_schur_reweight; include/vinsat_ba.h carries
-// the contract, the entry points and the handle live in vba_schur.hip) and the exact radix select behind it, which
-// vba_schur_median runs on caller keys.  The reference's weights (BA_filtering.py:21-25): c = the lower median of the 2 m values
-// |r|, q_k = mean over the two components of ((r / c)^2 / |alpha - 2| + 1)^(alpha / 2 - 1) / c^2, rho_k = q_k / max q, and
-// row_w[k] = rho_k * base_k.
+// vba_schur_robust.hip -- the free-landmark fit's robust re-weighting (vba_schur_reweight, vba_schur_get_weights; include/vinsat_ba.h
+// carries the contract, vba_schur_context.h the handle, vba_schur.hip the map of the units) and the exact radix select behind it, which
+// vba_schur_median runs on caller keys: the passes, then the entry points.  The reference's weights (BA_filtering.py:21-25):
+// c = the lower median of the 2 m values |r|, q_k = mean over the two components of ((r / c)^2 / |alpha - 2| + 1)^(alpha / 2 - 1) / c^2,
+// rho_k = q_k / max q, and row_w[k] = rho_k * base_k.
 //
 //   k_schur_robust_capture thread per row: base[k] = the weight the row was uploaded with (the saved one of a rejected row)
 //   k_schur_robust_keys    thread per row: the reprojection of the cost kernel at the resident state, |ru|, |rv| as one 16-byte store
@@ -18,10 +18,12 @@
 //                          positive and finite
 // Integer atomics only (histogram counts are exact in any order), a maximum for the one reduction: equal problems give equal bits.
 #include <algorithm>
+#include <mutex>
 
 #include <hip/hip_runtime.h>
 
 #include "vba_math.h"
+#include "vba_schur_context.h"
 #include "vba_schur_robust.h"
 
 namespace vba {
@@ -224,3 +226,164 @@ int schur_robust_launch(const SchurRobustView& V, double alpha, hipStream_t s) {
 }
 
 }  // namespace vba
+
+namespace {
+
+// one grow-only workspace per process for vba_schur_median (keys, the select's scratch, the result)
+struct MedianWorkspace {
+    std::mutex m;
+    int device = -1;
+    char* base = nullptr;
+    size_t size = 0;
+    hipStream_t stream = nullptr;
+} g_median_ws;
+
+}  // namespace
+
+// first re-weighting of a handle: its state and its two timing events
+static int schur_robust_alloc(vba_schur_handle h) {
+    SchurRobust& Z = h->robust;
+    if (Z.sc.arena) return VBA_OK;
+    const size_t m = (size_t)h->V.m;
+    SchurLayout lay;
+    const size_t o_b = lay.need(m * 8), o_k = lay.need(m * 16), o_q = lay.need(m * 8), o_p = lay.need((size_t)kRobustMaxBlocks * 8), o_r = lay.need(16),
+                 o_s = lay.need(schur_select_scratch_bytes());
+    if (int rc = schur_scratch_alloc(Z.sc, lay.bytes, "re-weighting state")) return rc;
+    char* A = Z.sc.arena;
+    Z.base = (double*)(A + o_b); Z.keys = (double*)(A + o_k); Z.q = (double*)(A + o_q); Z.part = (double*)(A + o_p); Z.res = (double*)(A + o_r);
+    Z.hist = (unsigned long long*)(A + o_s); Z.state = Z.hist + (size_t)kSelPasses * kSelBins;
+    Z.captured = Z.have_keys = false;
+    return VBA_OK;
+}
+
+static SchurRobustView schur_robust_view(vba_schur_handle h) {
+    const SchurView& V = h->V;
+    const SchurRobust& Z = h->robust;
+    SchurRobustView W{};
+    W.n = V.n; W.L = V.L; W.m = V.m;
+    W.row_pose = V.row_pose; W.row_lm = V.row_lm; W.row_u = V.row_u; W.row_v = V.row_v; W.intr = V.intr;
+    W.states = h->S0; W.X = h->X0buf;
+    W.row_w = const_cast<double*>(V.row_w);
+    W.saved = h->snoop.sc.arena ? h->snoop.saved : nullptr;
+    W.row_mask = h->snoop.sc.arena ? h->snoop.row_mask : nullptr;
+    W.base = Z.base; W.keys = Z.keys; W.q = Z.q; W.part = Z.part; W.res = Z.res;
+    W.sel.keys = reinterpret_cast<const unsigned long long*>(Z.keys); W.sel.count = 2 * V.m;
+    W.sel.hist = Z.hist; W.sel.state = Z.state; W.sel.out = Z.res;
+    return W;
+}
+
+extern "C" {
+
+int vba_schur_reweight(vba_schur_handle h, double alpha, double* c_obs, double* w_max, int* status) {
+    if (!h || !c_obs || !w_max || !status) return sfail(VBA_EINVAL, "null argument");
+    if (!(alpha >= 1.0 && alpha <= 2.0)) return sfail(VBA_EINVAL, "alpha must lie in [1, 2]");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_robust_alloc(h)) return rc;
+    SchurRobust& Z = h->robust;
+    hipStream_t s = h->stream;
+    const SchurRobustView W = schur_robust_view(h);
+    if (!Z.captured) {
+        schur_robust_capture_launch(W, s);
+        SCHK(hipGetLastError());
+        Z.captured = true;
+    }
+    SCHK(hipEventRecord(Z.sc.ev[0], s));
+    Z.launches = schur_robust_launch(W, alpha, s);
+    double res[2] = {0.0, 0.0};
+    const int rc = schur_scratch_finish(Z.sc, s, [&]() -> int {
+        SCHK(hipGetLastError());
+        SCHK(hipMemcpyAsync(res, Z.res, 16, hipMemcpyDeviceToHost, s));
+        return VBA_OK;
+    });
+    if (rc) return rc;
+    Z.have_keys = true;
+    const bool ok = res[0] > 0.0 && std::isfinite(res[0]) && res[1] > 0.0 && std::isfinite(res[1]);     // (the test of k_schur_robust_scale)
+    *c_obs = res[0];
+    *w_max = ok ? res[1] : std::nan("");
+    *status = ok ? 0 : 1;
+    return VBA_OK;
+}
+
+int vba_schur_get_weights(vba_schur_handle h, double* w, double* base) {
+    if (!h) return sfail(VBA_EINVAL, "null handle");
+    if (!h->uploaded) return sfail(VBA_ESTATE, "upload the problem first");
+    SCHK(hipSetDevice(h->device));
+    SCHK(hipStreamSynchronize(h->stream));
+    const size_t m = (size_t)h->V.m;
+    if (w) SCHK(hipMemcpy(w, h->V.row_w, m * 8, hipMemcpyDeviceToHost));
+    if (!base) return VBA_OK;
+    if (h->robust.sc.arena && h->robust.captured) {
+        SCHK(hipMemcpy(base, h->robust.base, m * 8, hipMemcpyDeviceToHost));
+        return VBA_OK;
+    }
+    SCHK(hipMemcpy(base, h->V.row_w, m * 8, hipMemcpyDeviceToHost));
+    if (h->snoop.sc.arena) {        // never re-weighted: the weights in place, a rejected row by its saved value
+        std::vector<double> saved;
+        std::vector<unsigned char> mask;
+        try {
+            saved.resize(m);
+            mask.resize(m);
+        } catch (const std::bad_alloc&) {
+            return sfail(VBA_ENOMEM, "host staging for vba_schur_get_weights failed");
+        }
+        SCHK(hipMemcpy(saved.data(), h->snoop.saved, m * 8, hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(mask.data(), h->snoop.row_mask, m, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < m; ++k) if (mask[k]) base[k] = saved[k];
+    }
+    return VBA_OK;
+}
+
+int vba_schur_last_reweight_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->robust.sc.ms;
+    return VBA_OK;
+}
+
+int vba_schur_median(int device, const double* keys, int64_t count, double* median) {
+    if (!keys || !median) return sfail(VBA_EINVAL, "null argument");
+    if (count < 1 || count > (int64_t)1 << 31) return sfail(VBA_EINVAL, "count must lie in [1, 2^31]");
+    for (int64_t k = 0; k < count; ++k)
+        if (std::isnan(keys[k]) || std::signbit(keys[k])) return sfail(VBA_EINVAL, "keys must be non-negative doubles (no NaN, no sign bit)");
+    int cnt = 0, prev = -1;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0) return sfail(VBA_ENODEV, "no HIP device visible");
+    if (device < 0 || device >= cnt) return sfail(VBA_EINVAL, "device index out of range");
+    std::lock_guard<std::mutex> lk(g_median_ws.m);
+    MedianWorkspace& G = g_median_ws;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    struct Back {                   // the caller's HIP device, whatever happens below
+        int dev;
+        ~Back() { if (dev >= 0) (void)hipSetDevice(dev); }
+    } back{prev};
+    SCHK(hipSetDevice(device));
+    const size_t kb = ((size_t)count * 8 + 255) & ~size_t(255), sb = (schur_select_scratch_bytes() + 255) & ~size_t(255);
+    const size_t need = kb + sb + 256;
+    if (G.device != device || G.size < need) {
+        if (G.base) (void)hipFree(G.base);
+        G.base = nullptr;
+        G.size = 0;
+        if (!G.stream || G.device != device) {
+            if (G.stream) (void)hipStreamDestroy(G.stream);
+            G.stream = nullptr;
+            G.device = -1;
+            SCHK(hipStreamCreateWithFlags(&G.stream, hipStreamNonBlocking));
+        }
+        if (hipMalloc(&G.base, need + need / 2) != hipSuccess) { (void)hipGetLastError(); G.base = nullptr; return sfail(VBA_ENOMEM, "hipMalloc of the median workspace failed"); }
+        G.size = need + need / 2;
+        G.device = device;
+    }
+    SchurSelectView W{};
+    W.keys = reinterpret_cast<const unsigned long long*>(G.base);
+    W.count = count;
+    W.hist = reinterpret_cast<unsigned long long*>(G.base + kb);
+    W.state = W.hist + (size_t)kSelPasses * kSelBins;
+    W.out = reinterpret_cast<double*>(G.base + kb + sb);
+    SCHK(hipMemcpyAsync(G.base, keys, (size_t)count * 8, hipMemcpyHostToDevice, G.stream));
+    schur_select_launch(W, G.stream, nullptr);
+    SCHK(hipGetLastError());
+    SCHK(hipMemcpyAsync(median, W.out, 8, hipMemcpyDeviceToHost, G.stream));
+    SCHK(hipStreamSynchronize(G.stream));
+    return VBA_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
-// vba_schur_snoop.h -- what vba_schur.hip (the handle, the entry points) and vba_schur_snoop.hip (the passes) share: the arrays the
-// passes of vba_schur_snoop read and write, and their launchers.  Internal.
+// vba_schur_snoop.h -- the arrays the passes of vba_schur_snoop (vba_schur_snoop.hip) read and write, and their launchers: what the
+// entry points fill from the handle (vba_schur_context.h) and the kernels take by value.  Internal.
 #pragma once
 
 #include <hip/hip_runtime.h>

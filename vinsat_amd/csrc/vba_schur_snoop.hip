@@ -1,5 +1,6 @@
-// vba_schur_snoop.hip -- the passes of free-landmark data snooping (vba_schur_snoop; include/vinsat_ba.h carries the contract, the
-// entry points and the handle live in vba_schur.hip).  They run behind the device part of vba_schur_reliability on the handle's
+// vba_schur_snoop.hip -- free-landmark data snooping (vba_schur_snoop, vba_schur_rejected, vba_schur_snoop_restore;
+// include/vinsat_ba.h carries the contract, vba_schur_context.h the handle, vba_schur.hip the map of the units): its passes, then the
+// entry points.  The passes run behind the device part of vba_schur_reliability on the handle's
 // stream and read what it left: wtest of every row, lm_wtest of every catalogue prior, fit[5] = s0sq.  At most one rejection per
 // group; the rule is vba_schur_snoop_pick.h.
 //
@@ -19,6 +20,7 @@
 #include <algorithm>
 
 #include "vba_device.h"
+#include "vba_schur_context.h"
 #include "vba_schur_snoop.h"
 #include "vba_schur_snoop_pick.h"
 
@@ -125,3 +127,128 @@ void schur_snoop_restore_launch(const SchurSnoopView& V, hipStream_t s) {
 }
 
 }  // namespace vba
+
+// first snoop of a handle: its state (masks cleared) and its two timing events
+static int schur_snoop_alloc(vba_schur_handle h) {
+    SchurSnoop& Z = h->snoop;
+    if (Z.sc.arena) return VBA_OK;
+    const SchurView& V = h->V;
+    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
+    SchurLayout lay;
+    const size_t o_sv = lay.need(m * 8), o_cr = lay.need(8), o_rm = lay.need(m), o_lk = lay.need(L), o_ld = lay.need(L * 4), o_pp = lay.need(n * 4),
+                 o_ps = lay.need(n * 4), o_po = lay.need(n * 4), o_lo = lay.need(L * 4);
+    if (int rc = schur_scratch_alloc(Z.sc, lay.bytes, "snooping state")) return rc;
+    char* A = Z.sc.arena;
+    Z.saved = (double*)(A + o_sv); Z.crit_used = (double*)(A + o_cr); Z.row_mask = (unsigned char*)(A + o_rm); Z.lm_mask = (unsigned char*)(A + o_lk);
+    Z.lm_dec = (int*)(A + o_ld); Z.pose_pick = (int*)(A + o_pp); Z.pose_short = (int*)(A + o_ps); Z.pose_out = (int*)(A + o_po); Z.lm_out = (int*)(A + o_lo);
+    std::fill(Z.totals, Z.totals + 3, 0);
+    return VBA_OK;
+}
+
+static SchurSnoopView schur_snoop_view(vba_schur_handle h) {
+    const SchurView& V = h->V;
+    const SchurSnoop& Z = h->snoop;
+    const SchurRel& R = h->rel;
+    SchurSnoopView W{};
+    W.n = V.n; W.L = V.L; W.m = V.m;
+    W.lm_ptr = V.lm_ptr; W.row_pose = V.row_pose; W.row_lm = V.row_lm; W.pose_ptr = V.pose_ptr; W.pose_rows = V.pose_rows;
+    W.row_w = const_cast<double*>(V.row_w);
+    W.wt = R.wt; W.lmwt = R.lmwt; W.fit = R.fit;
+    W.saved = Z.saved; W.row_mask = Z.row_mask; W.lm_mask = Z.lm_mask;
+    W.lm_dec = Z.lm_dec; W.pose_pick = Z.pose_pick; W.pose_short = Z.pose_short; W.pose_out = Z.pose_out; W.lm_out = Z.lm_out;
+    W.crit_used = Z.crit_used;
+    return W;
+}
+
+extern "C" {
+
+int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
+                    int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_snoop") + kDynRefusal);
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (!(crit >= 0.0)) return sfail(VBA_EINVAL, "crit must be >= 0 (+inf rejects nothing)");
+    if (min_rows < 0 || min_track < 0) return sfail(VBA_EINVAL, "min_rows and min_track must be >= 0");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    if (int rc = schur_query_index(h)) return rc;
+    if (int rc = schur_rel_alloc(h)) return rc;
+    if (int rc = schur_snoop_alloc(h)) return rc;
+    SchurSnoop& Z = h->snoop;
+    hipStream_t s = h->stream;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_rel_device(h, lamda, Z.sc.ev[0], V, &bad)) return rc;
+    *info = bad;
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    if (bad != 0) {                 // no factor, no test: nothing is rejected; the critical value of a fit that does not exist
+        if (int rc = schur_scratch_finish(Z.sc, s)) return rc;
+        if (crit_used) *crit_used = scaled ? std::nan("") : crit;
+        return VBA_OK;
+    }
+    const SchurSnoopView W = schur_snoop_view(h);
+    schur_snoop_launch(W, crit, scaled ? 1 : 0, min_rows, min_track, s);
+    std::vector<int> out;
+    double c = 0.0;
+    const int rc = schur_scratch_finish(Z.sc, s, [&]() -> int {
+        SCHK(hipGetLastError());
+        try {
+            out.resize((size_t)V.n + (size_t)V.L);
+        } catch (const std::bad_alloc&) {
+            return sfail(VBA_ENOMEM, "host staging for the counts of vba_schur_snoop failed");
+        }
+        SCHK(hipMemcpyAsync(out.data(), Z.pose_out, (size_t)V.n * 4, hipMemcpyDeviceToHost, s));
+        SCHK(hipMemcpyAsync(out.data() + V.n, Z.lm_out, (size_t)V.L * 4, hipMemcpyDeviceToHost, s));
+        SCHK(hipMemcpyAsync(&c, Z.crit_used, 8, hipMemcpyDeviceToHost, s));
+        return VBA_OK;
+    });
+    if (rc) return rc;
+    int now[3] = {0, 0, 0};
+    for (int i = 0; i < V.n; ++i) now[0] += out[i];
+    for (int l = 0; l < V.L; ++l)
+        if (out[(size_t)V.n + l] > 0) { now[1] += 1; now[2] += out[(size_t)V.n + l] - 1; }
+    for (int k = 0; k < 3; ++k) {
+        Z.totals[k] += now[k];
+        if (counts) counts[k] = now[k];
+    }
+    if (crit_used) *crit_used = c;
+    return VBA_OK;
+}
+
+int vba_schur_rejected(vba_schur_handle h, unsigned char* row_mask, unsigned char* lm_mask, int* totals) {
+    if (!h) return sfail(VBA_EINVAL, "null handle");
+    const SchurSnoop& Z = h->snoop;
+    if (totals) for (int k = 0; k < 3; ++k) totals[k] = Z.sc.arena ? Z.totals[k] : 0;
+    if (!Z.sc.arena) {
+        if (row_mask) std::memset(row_mask, 0, (size_t)h->V.m);
+        if (lm_mask) std::memset(lm_mask, 0, (size_t)h->V.L);
+        return VBA_OK;
+    }
+    SCHK(hipSetDevice(h->device));
+    SCHK(hipStreamSynchronize(h->stream));
+    if (row_mask) SCHK(hipMemcpy(row_mask, Z.row_mask, (size_t)h->V.m, hipMemcpyDeviceToHost));
+    if (lm_mask) SCHK(hipMemcpy(lm_mask, Z.lm_mask, (size_t)h->V.L, hipMemcpyDeviceToHost));
+    return VBA_OK;
+}
+
+int vba_schur_snoop_restore(vba_schur_handle h) {
+    if (!h) return sfail(VBA_EINVAL, "null handle");
+    SchurSnoop& Z = h->snoop;
+    if (!Z.sc.arena || (Z.totals[0] == 0 && Z.totals[1] == 0 && Z.totals[2] == 0)) return VBA_OK;
+    SCHK(hipSetDevice(h->device));
+    schur_snoop_restore_launch(schur_snoop_view(h), h->stream);
+    SCHK(hipGetLastError());
+    SCHK(hipMemsetAsync(Z.lm_mask, 0, (size_t)h->V.L, h->stream));
+    SCHK(hipStreamSynchronize(h->stream));
+    std::fill(Z.totals, Z.totals + 3, 0);
+    return VBA_OK;
+}
+
+int vba_schur_last_snoop_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->snoop.sc.ms;
+    return VBA_OK;
+}
+
+}  // extern "C"

@@ -4,7 +4,7 @@ The reference (CMUAbstract/VINSat) keeps its landmarks fixed (``estimation/BA/BA
 marginalise and no counterpart of this module in it.  This is the variant BASELINE.json's north_star describes on top of the
 reference's reprojection model: the landmarks become unknowns (3 each, held by a catalogue prior ``N(X0, sigma^2 I)``), the
 landmark blocks are eliminated (3x3 inversions), and the dense reduced camera system is factorised on the matrix cores
-(``vinsat_amd/csrc/vba_schur.hip``).  It is validated against ``oracle/schur_oracle.py`` -- this repository's own CPU
+(``vinsat_amd/csrc/vba_schur*.hip``, one unit per stage; ``vba_schur.hip`` heads them with the map).  It is validated against ``oracle/schur_oracle.py`` -- this repository's own CPU
 restatement -- only, and it never runs inside :func:`vinsat_amd.ba.BA`.  Opt-in per handle (``time_idx=``, ``sigma_dyn=``) the
 reference's J2 orbit factor ties consecutive poses and the velocities become unknowns (``vinsat_amd/csrc/vba_schur_dyn.hip``,
 DESIGN 9.5); the attitude factor is not part of it.
