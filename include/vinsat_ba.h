@@ -293,7 +293,8 @@ int vba_debug_fetch(vba_handle h, int window, int what, double* out, int64_t cap
  *   A      the undamped bands as VBA_DBG_BANDS defines them; damped != 0 adds float32(lamda_resident) I, the damping the next
  *          call's first trial would use (BA_filtering.py:54) -- that matrix is the reference's JTwJ;
  *   A^     (A + A^T) / 2: A is symmetric but for the 3x3 rot-rot diagonal blocks Sigma Hd of the attitude factor;
- *   diag   [W][n_max][9][9]  Sigma_ii = (A^-1)_ii, exactly symmetric (one triangle computed, mirrored);
+ *   diag   [W][n_max][9][9]  Sigma_ii = (A^-1)_ii, exactly symmetric (one triangle computed, mirrored); zeros for rows beyond n,
+ *          on both paths;
  *   super  [W][n_max][9][9]  Sigma_i,i+1 = (A^-1)_i,i+1 for i < n - 1 (zeros for i = n - 1 and for rows beyond n);
  *   flags  [W]  VBA_FLAG_ZERO_PIVOT: numerically singular (e.g. the velocities of a one-pose window, undamped): that window's blocks
  *               are NaN; VBA_FLAG_INDEFINITE: the blocks are returned but are no covariance; VBA_FLAG_NONFINITE as elsewhere.
