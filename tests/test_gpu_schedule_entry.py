@@ -168,8 +168,38 @@ def test_a_changed_handle_is_not_served_a_stale_graph(win):
         _same(got, want, k)
         _same(_run(a, win["st0"]), want, (k, "replay"))
         restore(a)
+        # the handle's generation has moved, but the views it yields are those of the base graph again: found by key and view
+        # bytes (no capture), which refreshes the graph's identity -- the schedule after it is matched by identity alone
+        captures, replays = a.schedule_graph_stats()
         _same(_run(a, win["st0"]), base, (k, "restored"))
+        assert a.schedule_graph_stats() == (captures, replays + 1), (k, "restored")
+        _same(_run(a, win["st0"]), base, (k, "restored, replay"))
+        assert a.schedule_graph_stats() == (captures, replays + 2), (k, "restored, replay")
     a.close()
+
+
+def test_the_ninth_schedule_evicts_the_least_recently_used_graph(win):
+    """A handle keeps eight graphs, most recently used first, and a ninth evicts the one at the back.  Even-length prefixes of the
+    driver's schedule (the call parity stays 0, and parity is part of a graph's identity); after every schedule the handle
+    holds what a handle with the graph switched off holds."""
+    a, b = _engine(win), _engine(win, graph=False)
+
+    def run(ncalls, want):
+        _same(_run(a, win["st0"], iters=ITERS[:ncalls], inits=INITS[:ncalls]),
+              _run(b, win["st0"], iters=ITERS[:ncalls], inits=INITS[:ncalls]), (ncalls, want))
+        assert a.schedule_graph_stats() == want, (ncalls, want)
+
+    for k, ncalls in enumerate(range(20, 2, -2)):       # nine graphs: the last one evicts the 20-call graph
+        run(ncalls, (k + 1, 0))
+    for k, ncalls in enumerate(range(18, 2, -2)):       # the other eight are there; the 18-call graph is now the least recently used
+        run(ncalls, (9, k + 1))
+    run(20, (10, 8))                                    # captured again, evicts the 18-call graph
+    run(18, (11, 8))                                    # ... which evicts the 16-call graph, used right after it
+    run(16, (12, 8))                                    # ... which evicts the 14-call graph
+    run(20, (12, 9))                                    # still there
+    assert b.schedule_graph_stats() == (0, 0)
+    a.close()
+    b.close()
 
 
 @pytest.mark.parametrize("step", [1, 2, 3], ids=["end-capture", "instantiate", "first-launch"])

@@ -409,7 +409,7 @@ int vba_destroy(vba_handle h) {
     if (h->own_stream) { hipStreamSynchronize(h->own_stream); hipStreamDestroy(h->own_stream); }
     if (h->aux_stream) { hipStreamSynchronize(h->aux_stream); hipStreamDestroy(h->aux_stream); }
     for (hipEvent_t e : h->cprof.ev) if (e) hipEventDestroy(e);
-    for (auto& ge : h->graphs) if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
+    h->gcache.destroy();
     if (h->ev_first) hipEventDestroy(h->ev_first);
     if (h->h_states_map) hipHostFree(h->h_states_map);
     if (h->h_stage_map) hipHostFree(h->h_stage_map);

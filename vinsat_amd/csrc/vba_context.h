@@ -1,8 +1,9 @@
 // vba_context.h -- the host side of libvinsat_ba.so shared by its translation units: the context behind a vba_handle, error
 // reporting, and the functions one file defines and another calls.
 //   vba_api.hip          context, options, uploads, states, diagnostics (vba_debug_fetch)
-//   vba_schedule.hip     the kernels of one BA() call as the host enqueues them: vba_step, vba_run_schedule (chained calls, graph
-//                        replay), vba_iterate* (pipelined driver loop, host watch)
+//   vba_call.hip         the kernels of one BA() call as the host enqueues them: vba_step, the rest of a stalled call
+//   vba_schedule.hip     vba_run_schedule (chained calls), the graph cache that replays its first pass, the chain profile
+//   vba_iterate.hip      vba_iterate* (states over PCIe, the pipelined driver loop, host watch)
 //   vba_sharded_api.hip  observation-sharded mode (vba_sh_*)
 //   vba_cov.hip          per-pose marginal covariances (vba_covariance); the step and the scaffold the three queries share
 //   vba_rel.hip          per-row leverages and w-tests (vba_reliability)
@@ -84,6 +85,30 @@ struct QueryScratch {
     hipEvent_t ev = nullptr;
     float ms = 0.f;
     bool ran = false;
+};
+
+// The first passes of the last few chained schedules as graphs (vba_run_schedule), each with what it was made for; most recently
+// used first, at most kCapacity of them (a driver alternates between a handful of schedules: the 20-call loop, its two phases).
+//   key    a hash per call's view (the quick reject)
+//   views  the bytes of those views, compared exactly on a key match (a 64-bit hash collision would replay another schedule's
+//          launches silently; ncalls x sizeof(DevView) of memcmp is ~1 us)
+//   ident  what the handle looked like when key and views were last found equal (pass_identity in vba_schedule.hip) -- a schedule
+//          that finds it unchanged replays without building a single view
+// Defined in vba_schedule.hip.
+struct GraphCache {
+    static constexpr size_t kCapacity = 8;
+    static constexpr size_t npos = ~size_t(0);
+    struct Entry { std::vector<unsigned long long> key, ident; std::vector<unsigned char> views; hipGraphExec_t exec = nullptr; };
+    std::vector<Entry> entries;
+    std::vector<unsigned long long> ident;      // identity of the pass being looked up (scratch, reused: a replay allocates nothing)
+    bool broken = false;                        // capture or launch failed once: kernel by kernel from then on
+    long captures = 0, replays = 0;
+    size_t find_ident() const;                  // the entry made for `ident`, or npos
+    size_t find_views(const std::vector<unsigned long long>& key, const std::vector<unsigned char>& views);    // ... for these views: a hit adopts `ident`
+    hipGraphExec_t use(size_t k);               // entry k moves to the front
+    // a new first entry for `ident`; a full cache drops its last one (once the stream s, where it may still execute, is idle)
+    int store(const std::vector<unsigned long long>& key, std::vector<unsigned char>&& views, hipGraphExec_t exec, hipStream_t s);
+    void destroy();                             // the graphs themselves (vba_destroy)
 };
 
 struct vba_context {
@@ -179,17 +204,9 @@ struct vba_context {
     int cr_levels = 2;                      // cyclic-reduction levels in front of the one-workgroup kernel (VBA_CR_LEVELS / vba_set_cr_levels: 2 or 3)
     int fusion = 15;                        // vba_set_fusion (default: the trial kernel forms the step, the solves form their own blocks, uniform-pass assembly)
     bool fusion_auto = true;                // the mask is the library's own choice (vba_set_fusion not called)
-    // the first passes of the last few chained schedules as graphs (vba_run_schedule), each with what it was made for; most recently
-    // used first, at most kGraphCache of them (a driver alternates between a handful of schedules: the 20-call loop, its two phases)
-    // key: a hash per call's view (the quick reject); views: the bytes of those views, compared exactly on a key match (a 64-bit hash
-    // collision would replay another schedule's launches silently; ncalls x sizeof(DevView) of memcmp is ~1 us)
-    // ident: what the handle looked like when key and views were last found equal (graph_ident in vba_schedule.hip) -- a schedule that
-    // finds it unchanged replays without building a single view
-    struct GraphEntry { std::vector<unsigned long long> key, ident; std::vector<unsigned char> views; hipGraphExec_t exec = nullptr; };
-    std::vector<GraphEntry> graphs;
-    std::vector<unsigned long long> ident_now;      // (scratch of vba_run_schedule: no allocation per call)
+    GraphCache gcache;
     // Generation of everything a DevView of view_for_call or a branch of the enqueue functions is made from, apart from what
-    // graph_ident lists itself.  touch() -- called by every entry point that can change one of them -- covers:
+    // pass_identity (vba_schedule.hip) lists itself.  touch() -- called by every entry point that can change one of them -- covers:
     //   h->V.*          every field of the handle's base view: chunk, chunk2 (vba_set_solver / _solver2), hop, nblk_long
     //                   (vba_set_integrator, vba_upload_window), acc_lanes, trial_tiles, warm_shift, bucket_cap, jac_f32 (vba_set_option),
     //                   n_min (vba_upload_observations), m_total, warm_shift (vba_sh_*), inv_sigma2 (Schur add-on)
@@ -202,9 +219,7 @@ struct vba_context {
     // replays a stale graph: a wrong result, not a slow one.
     unsigned long long gen = 0;
     void touch() { ++gen; }
-    bool graph_broken = false;              // capture or launch failed once: kernel by kernel from then on
     bool graph_enabled = true;              // vba_set_schedule_graph
-    long graph_replays = 0, graph_captures = 0;
     int bucket_cap_alloc = 0;               // allocated capacity of a bin bucket (vba_set_bucket_cap lowers the one in use)
     int warm_misses = 0;                    // number of calls whose warm select missed and was repeated with the exact digits (diagnostic)
     double* d_dbg = nullptr;                // lazily allocated scratch for debug fetch
@@ -268,27 +283,7 @@ int flush_states(vba_handle h);
 int ready(vba_handle h);
 void unpack_scalars(const WinScalars* sc, int par, double* lamda, double* last_hessian, int* n_trials, unsigned* flags);
 
-// ---- vba_schedule.hip
-// ---------------------------------------------------------------------------------------------- one BA() call
-// The kernels of a call, as the host enqueues them (all asynchronous on the handle's stream):
-//
-//   front   [k_obs_residual]                     only when the host replaced the states (no carried keys)
-//           [select]                             exact digits (2 passes; 3 when digit 0 is not there yet); on carried keys
-//                                                ONE warm pass (k_select_warm) -- or, latency mode, nothing: the keys lie
-//                                                in per-bin buckets and the accumulation selects in its prologue.  In a
-//                                                chained schedule the kernel that starts the call also evaluates the
-//                                                accept test of the call in front (fold)
-//           k_obs_accumulate (+ dynamics blocks) median finish, weights, per-pose normal equations [+ orbit / attitude factor]
-//           [k_assemble]                         only when something reads the bands from memory: batched windows, sharded
-//                                                mode, the sequential / always-pivoting solvers
-//   trial   [solve]                              full phase: chunk elimination (forming its own blocks in latency mode),
-//                                                cyclic reduction of the separators; landmark-only phase: nothing in
-//                                                latency mode (the trial kernel solves its 6x6 systems itself)
-//           k_trial                              step + retraction (latency mode) + trial residuals + next call's keys
-//   decide  [k_decide]                           own launch unless the next call's first kernel folds it
-//
-// Latency mode, landmark-only call: 2 kernels (accumulate, trial); full call: 6 (+ assembly, chunks, two
-// cyclic-reduction kernels).  Call parity p: input states S[p], trial states S[p ^ 1] (see WinScalars).
+// ---- vba_call.hip (one BA() call: the kernels and their order are described at the top of that file)
 struct CallSpec {
     bool host_out = false;  // pipelined vba_iterate_resident: trial states and last_hessian also go to mapped host memory
     int iter = 0, initialize = 0;
@@ -312,10 +307,28 @@ void view_for_call(vba_handle h, DevView& V, const CallSpec& c);
 int enqueue_front(vba_handle h, CallCtx& C, const CallSpec& c, bool exact_repeat, hipEvent_t* ev);
 void enqueue_trial(vba_handle h, CallCtx& C, const CallSpec& c, bool first, hipEvent_t ev_solve = nullptr, int solve_redo = -1);
 int step_impl(vba_handle h, int iter, int initialize, float* prof, bool emit = true, int readback = -1);
-void watch_stop(vba_handle h);
-void watch_quiesce(vba_handle h);
+int finish_stalled_call(vba_handle h, const CallSpec& q, const std::vector<int>& stall_at, long& trials);
+// Any error return while one of these is armed leaves a half-run call behind: counts in any histogram, states and carried keys that
+// nobody can vouch for.  pipelined (iterate_pipelined): the speculated call and what the loop learnt from the previous one go as well.
+struct CallAbandon {
+    vba_handle h; bool pipelined = false; bool armed = true;
+    ~CallAbandon() {
+        if (!armed) return;
+        h->need_hist_reset = true; h->have_state.assign(h->W, 0); h->carry_ok = 0;
+        if (pipelined) { h->spec.valid = false; h->prev_res_iter = -1; }
+    }
+};
+// ... whose histograms (an abandoned call may have left counts in any of them) the next call clears in front of its own kernels;
+// V: any view of the handle.  Nothing unless need_hist_reset.
+void clear_abandoned_hists(vba_handle h, const DevView& V, hipStream_t s);
+
+// ---- vba_schedule.hip
 int vba_set_schedule_graph(vba_handle h, int on);      // (options of vba_set_option that live with the schedule)
 int vba_set_chain_profile(vba_handle h, int on);
+
+// ---- vba_iterate.hip
+void watch_stop(vba_handle h);
+void watch_quiesce(vba_handle h);
 
 // ---- vba_cov.hip
 // The step the three queries share: the shadow front of a full-phase call and the selected inversion, into the scratch of the
