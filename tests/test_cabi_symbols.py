@@ -58,6 +58,38 @@ def test_no_gpu_is_reported_not_hidden(lib_path):
             BAEngine(16, 256)
 
 
+EINVAL = 1
+
+
+@pytest.mark.parametrize("windows,n_max,m_max,mode", [(0, 8, 300, -1), (1, 1, 300, -1), (1, 8, 0, -1), (1, 8, 2**30 + 1, -1),
+                                                      (1, 8, 300, 2), (1, 8, 300, -2)])
+def test_create_refuses_bad_arguments_before_it_looks_for_a_device(lib_path, windows, n_max, m_max, mode):
+    """The argument checks of vba_create_mode precede the device count: the same answer with and without a GPU, *out left null."""
+    from vinsat_amd import _lib
+    lib = _lib.load()
+    h = ctypes.c_void_p(1)
+    assert lib.vba_create_mode(0, windows, n_max, m_max, mode, ctypes.byref(h)) == EINVAL
+    assert not h.value
+
+
+def test_create_refuses_a_null_out(lib_path):
+    from vinsat_amd import _lib
+    assert _lib.load().vba_create_mode(0, 1, 8, 300, -1, None) == EINVAL
+
+
+def test_every_setter_refuses_a_null_handle(lib_path):
+    from vinsat_amd import _lib
+    lib = _lib.load()
+    for name, opt in _lib.OPT.items():
+        assert lib.vba_set_option(None, opt, 0) == EINVAL, name
+    assert lib.vba_set_solver(None, -1) == EINVAL
+    assert lib.vba_set_solver2(None, 8, 0) == EINVAL
+    assert lib.vba_set_integrator(None, 0) == EINVAL
+    assert lib.vba_set_stream(None, None, 0) == EINVAL
+    assert lib.vba_set_prior(None, 0) == EINVAL
+    assert lib.vba_set_host_watch(None, 0, None, None, 0) == EINVAL
+
+
 def test_one_hip_runtime_in_the_process_whichever_is_imported_first():
     """The wheel of PyTorch bundles its own HIP runtime; the library binds to that copy (vinsat_amd/_lib.py), so that a
     process that calls BA() on numpy arrays first and touches torch.cuda later does not end up with two ROCr instances

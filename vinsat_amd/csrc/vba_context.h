@@ -1,6 +1,10 @@
 // vba_context.h -- the host side of libvinsat_ba.so shared by its translation units: the context behind a vba_handle, error
 // reporting, and the functions one file defines and another calls.
-//   vba_api.hip          context, options, uploads, states, diagnostics (vba_debug_fetch)
+//   vba_api.hip          error reporting, settle / ready / read_heads, version and mode getters
+//   vba_handle.hip       vba_create*, vba_destroy: mode defaults, the device arena and its layout, host resources
+//   vba_options.hip      vba_set_option and the other setters, the counters beside them
+//   vba_upload.hip       observations, pose constants, priors and states up; states back
+//   vba_debug.hip        vba_debug_fetch
 //   vba_call.hip         the kernels of one BA() call as the host enqueues them: vba_step, the rest of a stalled call
 //   vba_schedule.hip     vba_run_schedule (chained calls), the graph cache that replays its first pass, the chain profile
 //   vba_iterate.hip      vba_iterate* (states over PCIe, the pipelined driver loop, host watch)
@@ -65,18 +69,6 @@ inline void entry_stamp(int k) {
 #define VBA_ESTAMP(k) ((void)0)
 #endif
 
-struct Arena {
-    char* base = nullptr;
-    size_t size = 0, used = 0;
-    template <class T>
-    T* take(size_t count) {
-        used = (used + 255) & ~size_t(255);
-        T* p = reinterpret_cast<T*>(base + used);
-        used += count * sizeof(T);
-        return p;
-    }
-};
-
 // What each uncertainty query keeps in the handle: its device scratch (grown on demand, never shrunk), the event behind its last
 // kernel, and the device time of its last call.
 struct QueryScratch {
@@ -117,7 +109,7 @@ struct vba_context {
     int64_t m_max = 0;
     hipStream_t own_stream = nullptr, stream = nullptr, aux_stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
-    Arena arena;
+    char* arena = nullptr;                  // one device allocation behind every buffer of V (arena_layout, vba_handle.hip)
     DevView V{};
     // mutable device pointers (DevView holds const views of some)
     int *d_n = nullptr, *d_m = nullptr, *d_steps = nullptr;
@@ -277,10 +269,18 @@ void fill_params(StepParams& p, int iter, int initialize);
 int check_window(vba_handle h, int window);
 int read_heads(vba_handle h);
 const volatile WinHead* head(vba_handle h, int w);
-hipError_t create_aux_stream(hipStream_t* s);
 int settle(vba_handle h, bool boundary = false, bool keep_staged = false);
-int flush_states(vba_handle h);
 int ready(vba_handle h);
+
+// ---- vba_handle.hip
+constexpr int kPartitionedWindowsMax = 1023;    // more windows than this: the sequential walk (measured: the comment over default_latency_mode)
+
+// ---- vba_options.hip
+int vba_set_accumulate_lanes(vba_handle h, int lanes);      // (behind vba_set_option; vba_create_mode sets the defaults through them)
+int vba_set_trial_tiles(vba_handle h, int tiles);
+
+// ---- vba_upload.hip
+int flush_states(vba_handle h);
 void unpack_scalars(const WinScalars* sc, int par, double* lamda, double* last_hessian, int* n_trials, unsigned* flags);
 
 // ---- vba_call.hip (one BA() call: the kernels and their order are described at the top of that file)

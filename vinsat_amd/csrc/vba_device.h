@@ -115,7 +115,7 @@ struct DevView {
     int fold;                       // this call's first kernel first evaluates the accept test of call - 1 (chained schedule)
     int pending_only;               // k_decide: only windows whose trial of this call is evaluated and not yet decided (sc.pending)
     int redo;                       // 1: this launch repeats the call for the windows whose warm select missed (sc.miss), others skip
-    int lat;                        // latency mode (few windows): fused kernels, see vba_api.hip
+    int lat;                        // latency mode (few windows): fused kernels, see vba_handle.hip
     int fuse_blocks;                // latency mode: the chunk elimination forms the blocks of its chunk itself (VBA_OPT_FUSION bit 1)
     int resident;                   // latency mode: the solve is one grid of producer and waiting consumer blocks (k_solve_resident;
                                     // VBA_OPT_FUSION bit 5: chunks + cyclic-reduction groups, bit 6: + the one-workgroup tail)

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_decide(DevView V, const double* trial_a
 }
 
 // latency mode with a partitioned chain whose chunk (blocks + staged inputs + elimination scratch) fits the LDS of a CU:
-// the chunk kernel forms its blocks itself and k_assemble is not launched (vba_api.hip asks the same question)
+// the chunk kernel forms its blocks itself and k_assemble is not launched (vba_call.hip asks the same question)
 // ... and the sequential walk of the batched mode forms them pose by pose (VBA_OPT_FUSION bit 2)
 #ifdef VBA_VARIANTS
 bool walk_forms_blocks(const DevView& V) { return !V.lat && V.fuse_walk && !V.prm.initialize && V.chunk <= 0 && V.pack != 1; }
