@@ -639,7 +639,8 @@ int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t cap
  * (S, g and the factor's arrays are re-sized), lamda goes on the velocity diagonal too, vba_schur_get_state returns the updated
  * velocities, and the build time of vba_schur_last_ms includes the factor's kernels.  vba_schur_reweight, vba_schur_get_weights
  * and vba_schur_median work unchanged; vba_schur_covariance, vba_schur_reliability and vba_schur_snoop return VBA_ESTATE on such a
- * handle (their redundancy counts and gathers assume the 6 n system).  A handle that never calls this behaves as before.
+ * handle (their redundancy counts and gathers assume the 6 n system); vba_schur_covariance_dyn is its covariance query.  A handle
+ * that never calls this behaves as before.
  * Errors: VBA_EINVAL for n < 2, a gap outside 1 .. 64, a time_idx that does not increase, a sigma_dyn that is not positive and
  * finite; VBA_ESTATE before the upload or on a handle that has the factor already. */
 int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx /*[n]*/, double sigma_dyn);
@@ -665,6 +666,30 @@ int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov /*[n
                          double* lm_cov /*[L][3][3] or NULL*/, int* info);
 /* HIP-event time of the last vba_schur_covariance on this handle (build, factorisation, selected inverse and gathers) */
 int vba_schur_last_covariance_ms(vba_schur_handle h, float* ms);
+/* State covariances on a handle with the dynamics factor (vba_schur_enable_dynamics), at the resident state: blocks of the inverse
+ * of H = [[B9, E9], [E9^T, C]] as vba_schur_iterate(h, lamda, ...) builds it on such a handle (the dynamics blocks and lamda on
+ * the velocity diagonal included).  S9 = B9 - E9 C^-1 E9^T is ordered [6 n pose | 3 n velocity]; with x_i = [dp (km), dtheta,
+ * dv (km/s)] of pose i -- the coordinates of vba_covariance -- component c of x_i is unknown u(i, c) = 6 i + c for c < 6 and
+ * 6 n + 3 i + (c - 6) for c >= 6.
+ *   state_cov[i] = the 9x9 marginal of x_i: the entries of S9^-1 at u(i, .); the lower triangle is read and mirrored, so every
+ *                  block is exactly symmetric, and state_cov[i][:6][:6] has the bits of the diagonal block i of pair_cov;
+ *   edge_cov[i]  = Sigma(x_i, x_{i+1}), rows of pose i and columns of pose i + 1 (the super-diagonal convention of vba_covariance):
+ *                  what propagating or differencing consecutive states needs;
+ *   pair_cov[b], lm_cov[l]: as vba_schur_covariance defines them, the 6x6 blocks out of the pose part (top-left 6 n x 6 n) of
+ *                  S9^-1 (E9 has no velocity rows: the landmark formula is unchanged).
+ * state_cov and edge_cov are required, pair_cov and lm_cov may be NULL.  *info as for vba_schur_covariance: 0, or 1 + the first
+ * row with a non-positive pivot; then every output is filled with NaN and the call returns VBA_OK.  VBA_EINVAL: null handle,
+ * info, state_cov or edge_cov, lamda negative or NaN; VBA_ESTATE: before upload or before a state is set, or a handle without
+ * the dynamics factor (vba_schur_covariance is the query of those; it, vba_schur_reliability and vba_schur_snoop keep refusing
+ * a handle that has the factor).  The query changes nothing: it builds and factorises into scratch of its own, the residuals,
+ * Jacobians and edge costs of its build included, so vba_schur_debug_fetch 3 .. 6 still report the last iterate; the following
+ * iterates return the bits they would have returned without it.  Fixed order of operations: equal bits for equal problems.  Only
+ * the tiles of S9^-1 that an output reads are formed; VBA_SCHUR_COV_FULL=1 in the environment at vba_schur_create forms all of
+ * them by the kernel of vba_schur_covariance (comparison: the outputs have the same bits either way). */
+int vba_schur_covariance_dyn(vba_schur_handle h, double lamda, double* state_cov /*[n][9][9]*/, double* edge_cov /*[n-1][9][9]*/,
+                             double* pair_cov /*[nblk][6][6] or NULL*/, double* lm_cov /*[L][3][3] or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_covariance_dyn on this handle (build, factorisation, selected inverse and gathers) */
+int vba_schur_last_covariance_dyn_ms(vba_schur_handle h, float* ms);
 /* Reliability of the free-landmark fit at the resident state: which observation row, and which catalogue position, the window
  * contradicts.  H, S, Y_k and the covariance blocks are those of vba_schur_covariance(h, lamda, ...); Sigma = H^-1.  For row k
  * (landmark-sorted order as uploaded; pose i, landmark l) with A_k = d uv / d [dp, dtheta] (2x6), Al_k = d uv / d X = -A_k[:, :3],

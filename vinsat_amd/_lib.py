@@ -96,6 +96,8 @@ SIGNATURES = {
     "vba_schur_enable_dynamics": (c_int, [c_void_p, POINTER(c_int), c_double]),
     "vba_schur_covariance": (c_int, [c_void_p, c_double, PD, PD, PD, POINTER(c_int)]),
     "vba_schur_last_covariance_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_covariance_dyn": (c_int, [c_void_p, c_double, PD, PD, PD, PD, POINTER(c_int)]),
+    "vba_schur_last_covariance_dyn_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_reliability": (c_int, [c_void_p, c_double, PD, PD, PD, PD, PD, PD, PD, POINTER(c_int)]),
     "vba_schur_last_reliability_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_snoop": (c_int, [c_void_p, c_double, c_double, c_int, c_int, c_int, POINTER(c_int), PD, POINTER(c_int)]),

@@ -19,7 +19,8 @@
 //   vba_schur.hip         this file: the handle's lifecycle, one LM trial (vba_schur_iterate), substitutions, update, cost
 //   vba_schur_build.hip   k_lm_blocks, k_pose_blocks, k_pair_blocks, k_pad_identity
 //   vba_schur_factor.hip  k_potrf64, k_potrf64b, k_gemm_abt, k_syrk_panel and the order of their launches
-//   vba_schur_cov.hip     vba_schur_covariance: k_trinv_step, k_syrk_wtw, k_cov_gather, k_lm_cov
+//   vba_schur_cov.hip     vba_schur_covariance: k_trinv_step, k_syrk_wtw, k_cov_gather, k_lm_cov; vba_schur_covariance_dyn on top:
+//                         k_syrk_wtw_sel, k_state_gather (index map and tile list: vba_schur_dyn_cov.h)
 //   vba_schur_rel.hip     vba_schur_reliability: k_rel_rows, k_rel_stats, k_rel_totals
 //   vba_schur_snoop.hip   vba_schur_snoop, vba_schur_rejected, vba_schur_snoop_restore and their passes
 //   vba_schur_robust.hip  vba_schur_reweight, vba_schur_get_weights, vba_schur_median and their passes
@@ -39,6 +40,9 @@
 //   k_syrk_wtw      S^-1 = W^T W on the matrix cores, block per tile of the lower triangle
 //   k_cov_gather    the listed 6x6 blocks of S^-1 (pair_cov) and its diagonal blocks (pose_cov)
 //   k_lm_cov        thread per landmark: C_l^-1 + sum Y_k^T Sigma_{pose(k), pose(k')} Y_k'
+// State covariances of a handle with the dynamics factor (vba_schur_covariance_dyn: build, factor, k_trinv_step as above, then)
+//   k_syrk_wtw_sel  the tiles of S9^-1 = W^T W that an output reads, block per listed tile, the bits of k_syrk_wtw
+//   k_state_gather  the 9x9 blocks [dp, dtheta, dv] of every pose and of every pair of consecutive poses
 // Reliability query (vba_schur_reliability: the device part of the covariance query, then)
 //   k_rel_rows      thread per row: pose-landmark cross-covariance Sigma_il from the gathered blocks and Y, leverage and w-test
 //   k_rel_stats     thread per landmark / per pose: their rows' statistics; the catalogue prior of a landmark as an observation
@@ -205,12 +209,13 @@ static int schur_cost(vba_schur_handle h, const double* states, const double* X,
 
 // Build the reduced camera system of the view's state and damping and factorise it, on stream s (the bulk of a panel's trailing
 // update beside it on h->aux): S, g, Cinv, wl, E, Y, invL and *d_info are the view's and the caller's, so vba_schur_iterate runs it
-// on the handle's arrays and vba_schur_covariance on scratch of its own.  ev_built (if given) is recorded between the two parts.
-int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built) {
+// on the handle's arrays and vba_schur_covariance on scratch of its own.  ev_built (if given) is recorded between the two parts;
+// dyn (if given) stands for the handle's dynamics arrays in the build.
+int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn) {
     SCHK(hipMemsetAsync(V.S, 0, (size_t)V.Npad * V.Npad * 8, s));
     SCHK(hipMemsetAsync(V.g, 0, (size_t)V.Npad * 8, s));
     SCHK(hipMemsetAsync(d_info, 0, 4, s));
-    schur_build_launch(h, V, s);
+    schur_build_launch(h, V, s, dyn);
     if (ev_built) SCHK(hipEventRecord(ev_built, s));
     return schur_factor_launch(h, V, s, d_info);
 }
@@ -268,6 +273,7 @@ int vba_schur_create(int device, int n, int64_t m, int L, int nblk, int64_t npai
               hipEventCreateWithFlags(&h->ev_chain, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&h->ev_bulk, hipEventDisableTiming) == hipSuccess;
     if (const char* e = std::getenv("VBA_SCHUR_CLASSIC")) h->classic = std::atoi(e);
+    if (const char* e = std::getenv("VBA_SCHUR_COV_FULL")) h->cov_full = std::atoi(e);
     for (int k = 0; k < 5 && ok; ++k) ok = hipEventCreate(&h->ev[k]) == hipSuccess;
     if (!ok) { vba_schur_destroy(h); return sfail(VBA_EHIP, "stream / event creation failed"); }
     *out = h;

@@ -139,12 +139,12 @@ __global__ void k_pad_identity(SchurView V) {
 
 }  // namespace
 
-void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s) {
+void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn) {
     hipLaunchKernelGGL(k_lm_blocks, dim3((V.L + 255) / 256), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pose_blocks, dim3((V.n + 15) / 16), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pair_blocks, dim3(V.nblk), dim3(64), 0, s, V);
-    if (h->dyn.enabled) {       // the dynamics blocks on top of the reprojection blocks (the queries never come here with the factor on)
-        const SchurDynView W = schur_dyn_view(h, V);
+    if (h->dyn.enabled) {       // the dynamics blocks on top of the reprojection blocks (vba_schur_covariance_dyn brings arrays of its own)
+        const SchurDynView W = dyn ? *dyn : schur_dyn_view(h, V);
         schur_dyn_edges_launch(W, V.states, s);
         schur_dyn_scatter_launch(W, s);
     }

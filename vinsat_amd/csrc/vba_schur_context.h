@@ -161,6 +161,12 @@ struct SchurQuery {
     double *W = nullptr, *pair = nullptr, *pose = nullptr, *lm = nullptr;
     int *info = nullptr, *lp_ptr = nullptr, *lp_blk = nullptr;
     bool indexed = false;
+    // on a handle with the dynamics factor (vba_schur_covariance_dyn): the 9x9 state and edge blocks, the tiles of the selected
+    // product (I, J per tile; built with the index, once per upload), and the dynamics arrays of the query's own build -- the
+    // handle's r, A, ecost stay those of its last iterate
+    double *state = nullptr, *edge = nullptr, *dyn_r = nullptr, *dyn_A = nullptr, *dyn_ecost = nullptr, *dyn_part = nullptr;
+    int* tiles = nullptr;
+    int ntiles = 0;
 };
 
 // What vba_schur_reliability needs beyond that, allocated by the first reliability query of a handle: its outputs on the device,
@@ -204,7 +210,7 @@ struct SchurDyn {
     std::vector<double> h_part;
 };
 
-// why the three queries refuse a handle with the dynamics factor
+// why the three queries refuse a handle with the dynamics factor (vba_schur_covariance_dyn is the covariance query of such a handle)
 constexpr char kDynRefusal[] = " is not available on a handle with the dynamics factor: its redundancy counts and gathers assume the "
                                "6 n reduced system of the reprojection rows";
 
@@ -216,6 +222,7 @@ struct vba_schur_context {
     hipEvent_t ev[5] = {};
     hipEvent_t ev_chain = nullptr, ev_bulk = nullptr;
     int classic = 0;                // VBA_SCHUR_CLASSIC=1: the round-2 tile-by-tile factorisation (comparison)
+    int cov_full = 0;               // VBA_SCHUR_COV_FULL=1: vba_schur_covariance_dyn runs the full W^T W product (comparison)
     int* d_info = nullptr;
     int last_info = 0;              // 0, or 1 + the row at which the last factorisation met a non-positive pivot
     double* S0 = nullptr;       // states buffers
@@ -236,8 +243,9 @@ struct vba_schur_context {
 
 // ---- vba_schur_build.hip
 // S, g, Cinv, wl, E, Y of the view's state and damping on stream s (S and g zeroed by the caller): the reprojection blocks, the
-// dynamics blocks on a handle with the factor, the identity of the padding rows
-void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s);
+// dynamics blocks on a handle with the factor, the identity of the padding rows.  dyn (if given) replaces the handle's own dynamics
+// arrays: the covariance query of such a handle builds r, A, ecost in its scratch and leaves the handle's as the last iterate wrote them
+void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn = nullptr);
 
 // ---- vba_schur_factor.hip
 // S = Lg Lg^T in place and the inverse diagonal factors, on stream s (the bulk of a panel's trailing update beside it on h->aux);
@@ -245,7 +253,7 @@ void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s);
 int schur_factor_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info);
 
 // ---- vba_schur.hip
-int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built);
+int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn = nullptr);
 
 // ---- vba_schur_cov.hip
 int schur_query_alloc(vba_schur_handle h);

@@ -1,7 +1,9 @@
 // vba_schur_cov.hip -- the covariance query of the free-landmark mode (vba_schur_covariance; include/vinsat_ba.h carries the
 // contract): build and factor into scratch of its own, then the selected blocks of the inverse.  Its device part is what
-// vba_schur_reliability and vba_schur_snoop start with.  vba_schur.hip carries the map of the units.
+// vba_schur_reliability and vba_schur_snoop start with.  vba_schur_covariance_dyn, the query of a handle with the dynamics factor,
+// follows it: the same stages over [6 n pose | 3 n velocity] unknowns.  vba_schur.hip carries the map of the units.
 #include "vba_schur_context.h"
+#include "vba_schur_dyn_cov.h"
 
 namespace {
 
@@ -75,17 +77,13 @@ __global__ __launch_bounds__(256) void k_trinv_step(SchurView V, double* W, int 
             for (int i = 0; i < 4; ++i) Wij[(size_t)(r0 + 16 * x + lk + 4 * i) * ld + c0 + 16 * y + lr] = -out[x][y][i];
 }
 
-// Tile (I, J), I >= J, of S^-1 = W^T W:  sum_{K = I}^{nbu - 1} W_KI^T W_KJ  (W_KI = 0 above the diagonal), K upwards, one block per
-// tile of the lower triangle (enumerated as k_gemm_abt<1> does); diagonal tiles are stored whole.  out may be the array the factor
-// lived in: W is all this kernel reads.
-__global__ __launch_bounds__(256) void k_syrk_wtw(SchurView V, const double* W, double* out, int nbu) {
+// Tile (I, J), I >= J, of S^-1 = W^T W:  sum_{K = I}^{nbu - 1} W_KI^T W_KJ  (W_KI = 0 above the diagonal), K upwards, by one block;
+// diagonal tiles are stored whole.  out may be the array the factor lived in: W is all this reads.  The one body of k_syrk_wtw and
+// k_syrk_wtw_sel: a tile has the same bits from either.
+__device__ __forceinline__ void syrk_wtw_tile(const SchurView& V, const double* W, double* out, int nbu, int I, int J) {
     __shared__ double As[kT][kT + 1];
     __shared__ double Bs[kT][kT + 1];
-    const int t = threadIdx.x, q = blockIdx.x;
-    int I = (int)((sqrt(8.0 * q + 1.0) - 1.0) * 0.5);
-    while ((I + 1) * (I + 2) / 2 <= q) ++I;
-    while (I * (I + 1) / 2 > q) --I;
-    const int J = q - I * (I + 1) / 2;
+    const int t = threadIdx.x;
     const size_t ld = (size_t)V.Npad;
     const int lane = t & 63, wv = t >> 6, r0 = (wv >> 1) * 32, c0 = (wv & 1) * 32, lr = lane & 15, lk = lane >> 4;
     vf4 acc[2][2];
@@ -107,6 +105,33 @@ __global__ __launch_bounds__(256) void k_syrk_wtw(SchurView V, const double* W, 
         for (int y = 0; y < 2; ++y)
 #pragma unroll
             for (int i = 0; i < 4; ++i) Cp[(size_t)(r0 + 16 * x + lk + 4 * i) * ld + c0 + 16 * y + lr] = acc[x][y][i];
+}
+
+// every tile of the lower triangle, one block each (enumerated as k_gemm_abt<1> does)
+__global__ __launch_bounds__(256) void k_syrk_wtw(SchurView V, const double* W, double* out, int nbu) {
+    const int q = blockIdx.x;
+    int I = (int)((sqrt(8.0 * q + 1.0) - 1.0) * 0.5);
+    while ((I + 1) * (I + 2) / 2 <= q) ++I;
+    while (I * (I + 1) / 2 > q) --I;
+    syrk_wtw_tile(V, W, out, nbu, I, q - I * (I + 1) / 2);
+}
+
+// The listed tiles only (tiles: I, J per tile, I >= J, both below nbu -- schur_dyn_cov_tiles), one block each.  The other tiles of
+// out keep what was there (the factor) and are never read.
+__global__ __launch_bounds__(256) void k_syrk_wtw_sel(SchurView V, const double* W, double* out, int nbu, const int* tiles) {
+    syrk_wtw_tile(V, W, out, nbu, tiles[2 * blockIdx.x], tiles[2 * blockIdx.x + 1]);
+}
+
+// The 9x9 blocks of vba_schur_covariance_dyn, thread per entry: state[i] = Sigma(x_i, x_i) and edge[i] = Sigma(x_i, x_{i+1}) over
+// x = [dp, dtheta, dv], read from the stored lower triangle of S9^-1 through the map of vba_schur_dyn_cov.h.  A state block is
+// exactly symmetric (both mirror entries read one stored entry), and its pose part has the bits k_cov_gather gives pose_cov.
+__global__ __launch_bounds__(256) void k_state_gather(SchurView V, const double* Sinv, double* state, double* edge) {
+    const int e = blockIdx.x * 256 + threadIdx.x, ns = 81 * V.n;
+    if (e >= 81 * (2 * V.n - 1)) return;
+    const SchurEntry s = schur_state_gather_entry(V.n, e);
+    const double v = Sinv[(size_t)s.r * V.Npad + s.c];
+    if (e < ns) state[e] = v;
+    else edge[e - ns] = v;
 }
 
 // The listed 6x6 blocks (i >= j) of S^-1 in block-list order, thread per entry; a diagonal block is read from its lower triangle
@@ -190,8 +215,18 @@ int schur_query_alloc(vba_schur_handle h) {
                  o_g = lay.need((size_t)V.Npad * 8), o_y = lay.need((size_t)V.Npad * 8), o_iL = lay.need((size_t)V.nb * kT * kT * 8),
                  o_dl = lay.need(L * 24), o_W = lay.need(NN), o_pair = lay.need((size_t)V.nblk * 288), o_pose = lay.need((size_t)V.n * 288),
                  o_lm = lay.need(L * 72), o_info = lay.need(256), o_lpp = lay.need((L + 1) * 4), o_lpb = lay.need((size_t)h->npairs * 4);
+    // a handle with the dynamics factor (V.Npad is 9 n based there): the outputs of vba_schur_covariance_dyn, the tile list of its
+    // selected product (at most every tile that holds unknowns) and the dynamics arrays of its build
+    const bool dyn = h->dyn.enabled;
+    const size_t ne = dyn ? (size_t)V.n - 1 : 0, nbu = (size_t)(V.N + kT - 1) / kT;
+    const size_t o_st = lay.need(dyn ? (size_t)V.n * 648 : 0), o_ed = lay.need(ne * 648), o_tl = lay.need(dyn ? nbu * (nbu + 1) * 4 : 0),
+                 o_dr = lay.need(ne * 48), o_dA = lay.need(ne * 288), o_de = lay.need(ne * 8), o_dp = lay.need(dyn ? (size_t)h->dyn.npart * 8 : 0);
     if (int rc = schur_scratch_alloc(Q.sc, lay.bytes, "query scratch")) return rc;
     char* A = Q.sc.arena;
+    if (dyn) {
+        Q.state = (double*)(A + o_st); Q.edge = (double*)(A + o_ed); Q.tiles = (int*)(A + o_tl);
+        Q.dyn_r = (double*)(A + o_dr); Q.dyn_A = (double*)(A + o_dA); Q.dyn_ecost = (double*)(A + o_de); Q.dyn_part = (double*)(A + o_dp);
+    }
     Q.Cinv = (double*)(A + o_ci); Q.wl = (double*)(A + o_wl); Q.E = (double*)(A + o_E); Q.Y = (double*)(A + o_Y); Q.S = (double*)(A + o_S);
     Q.g = (double*)(A + o_g); Q.ybuf = (double*)(A + o_y); Q.invL = (double*)(A + o_iL); Q.dl = (double*)(A + o_dl); Q.W = (double*)(A + o_W);
     Q.pair = (double*)(A + o_pair); Q.pose = (double*)(A + o_pose); Q.lm = (double*)(A + o_lm); Q.info = (int*)(A + o_info);
@@ -238,8 +273,24 @@ int schur_query_index(vba_schur_handle h) {
     for (int i = 0; i < V.n; ++i) if (!has_diag[i]) return sfail(VBA_EINVAL, "the block list lacks a diagonal block");
     SCHK(hipMemcpy(Q.lp_ptr, lp_ptr.data(), lp_ptr.size() * 4, hipMemcpyHostToDevice));
     SCHK(hipMemcpy(Q.lp_blk, lp_blk.data(), np * 4, hipMemcpyHostToDevice));
+    if (h->dyn.enabled) {       // the tiles of S9^-1 the outputs of vba_schur_covariance_dyn read (the block list was checked at the upload)
+        std::vector<int> tiles;
+        schur_dyn_cov_tiles(V.n, V.nblk, bi.data(), bj.data(), kT, tiles);
+        SCHK(hipMemcpy(Q.tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
+        Q.ntiles = (int)(tiles.size() / 2);
+    }
     Q.indexed = true;
     return VBA_OK;
+}
+
+// the view a query builds: the handle's problem at its resident state and this damping, everything written in the query's scratch
+static SchurView query_view(vba_schur_handle h, double lamda) {
+    const SchurQuery& Q = h->q;
+    SchurView V = h->V;
+    V.lamda = lamda;
+    V.states = h->S0; V.X = h->X0buf; V.states_new = nullptr; V.X_new = nullptr; V.part = nullptr;
+    V.Cinv = Q.Cinv; V.wl = Q.wl; V.E = Q.E; V.Y = Q.Y; V.S = Q.S; V.g = Q.g; V.ybuf = Q.ybuf; V.invL = Q.invL; V.dl = Q.dl;
+    return V;
 }
 
 // The device part of vba_schur_covariance, shared with vba_schur_reliability: ev_begin, then build and factorise into the query's
@@ -249,10 +300,7 @@ int schur_query_index(vba_schur_handle h) {
 int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad) {
     SchurQuery& Q = h->q;
     hipStream_t s = h->stream;
-    V = h->V;
-    V.lamda = lamda;
-    V.states = h->S0; V.X = h->X0buf; V.states_new = nullptr; V.X_new = nullptr; V.part = nullptr;
-    V.Cinv = Q.Cinv; V.wl = Q.wl; V.E = Q.E; V.Y = Q.Y; V.S = Q.S; V.g = Q.g; V.ybuf = Q.ybuf; V.invL = Q.invL; V.dl = Q.dl;
+    V = query_view(h, lamda);
     SCHK(hipEventRecord(ev_begin, s));
     if (int rc = schur_build_factor(h, V, s, Q.info, nullptr)) return rc;
     SCHK(hipGetLastError());
@@ -269,7 +317,74 @@ int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_
     return VBA_OK;
 }
 
+// The device part of vba_schur_covariance_dyn, as schur_query_device but on a handle with the dynamics factor: the dynamics blocks
+// of the build go through arrays of the scratch (DW), W is needed in full (h->bw = nb - 1: nothing skipped), then the listed tiles
+// of S9^-1 (every tile with VBA_SCHUR_COV_FULL=1), the 9x9 blocks, and k_cov_gather / k_lm_cov as they are: they index by V.Npad
+// and read the top-left 6 n x 6 n only (E9 has no velocity rows, so the landmark formula stands).
+static int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad) {
+    SchurQuery& Q = h->q;
+    hipStream_t s = h->stream;
+    V = query_view(h, lamda);
+    SchurDynView DW = schur_dyn_view(h, V);
+    DW.r = Q.dyn_r; DW.A = Q.dyn_A; DW.ecost = Q.dyn_ecost; DW.part = Q.dyn_part;
+    SCHK(hipEventRecord(ev_begin, s));
+    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr, &DW)) return rc;
+    SCHK(hipGetLastError());
+    *bad = 0;
+    SCHK(hipMemcpyAsync(bad, Q.info, 4, hipMemcpyDeviceToHost, s));
+    SCHK(hipStreamSynchronize(s));
+    if (*bad != 0) return VBA_OK;
+    const int nbu = (V.N + kT - 1) / kT;
+    const size_t n_pair = (size_t)V.nblk * 36;
+    for (int d = 0; d < nbu; ++d) hipLaunchKernelGGL(k_trinv_step, dim3(nbu - d), dim3(256), 0, s, V, Q.W, d, h->bw);
+    if (h->cov_full) hipLaunchKernelGGL(k_syrk_wtw, dim3(nbu * (nbu + 1) / 2), dim3(256), 0, s, V, Q.W, Q.S, nbu);
+    else hipLaunchKernelGGL(k_syrk_wtw_sel, dim3(Q.ntiles), dim3(256), 0, s, V, Q.W, Q.S, nbu, Q.tiles);
+    hipLaunchKernelGGL(k_state_gather, dim3((81 * (2 * V.n - 1) + 255) / 256), dim3(256), 0, s, V, Q.S, Q.state, Q.edge);
+    hipLaunchKernelGGL(k_cov_gather, dim3((unsigned)((n_pair + 255) / 256)), dim3(256), 0, s, V, Q.S, Q.pair, Q.pose);
+    if (with_lm) hipLaunchKernelGGL(k_lm_cov, dim3((V.L + 255) / 256), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm);
+    return VBA_OK;
+}
+
 extern "C" {
+
+int vba_schur_covariance_dyn(vba_schur_handle h, double lamda, double* state_cov, double* edge_cov, double* pair_cov, double* lm_cov, int* info) {
+    if (!h || !info || !state_cov || !edge_cov) return sfail(VBA_EINVAL, "null argument");
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    if (!h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    if (int rc = schur_query_index(h)) return rc;
+    SchurQuery& Q = h->q;
+    hipStream_t s = h->stream;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_query_device_dyn(h, lamda, lm_cov != nullptr, Q.sc.ev[0], V, &bad)) return rc;
+    *info = bad;
+    const size_t n_state = (size_t)V.n * 81, n_edge = (size_t)(V.n - 1) * 81, n_pair = (size_t)V.nblk * 36, n_lm = (size_t)V.L * 9;
+    if (bad != 0) {                 // no factor, no covariance: NaN, and the row in *info
+        if (int rc = schur_scratch_finish(Q.sc, s)) return rc;
+        std::fill(state_cov, state_cov + n_state, std::nan(""));
+        std::fill(edge_cov, edge_cov + n_edge, std::nan(""));
+        if (pair_cov) std::fill(pair_cov, pair_cov + n_pair, std::nan(""));
+        if (lm_cov) std::fill(lm_cov, lm_cov + n_lm, std::nan(""));
+        return VBA_OK;
+    }
+    return schur_scratch_finish(Q.sc, s, [&]() -> int {
+        SCHK(hipGetLastError());
+        SCHK(hipMemcpyAsync(state_cov, Q.state, n_state * 8, hipMemcpyDeviceToHost, s));
+        SCHK(hipMemcpyAsync(edge_cov, Q.edge, n_edge * 8, hipMemcpyDeviceToHost, s));
+        if (pair_cov) SCHK(hipMemcpyAsync(pair_cov, Q.pair, n_pair * 8, hipMemcpyDeviceToHost, s));
+        if (lm_cov) SCHK(hipMemcpyAsync(lm_cov, Q.lm, n_lm * 8, hipMemcpyDeviceToHost, s));
+        return VBA_OK;
+    });
+}
+
+int vba_schur_last_covariance_dyn_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->q.sc.ms;
+    return VBA_OK;
+}
 
 int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov, double* pair_cov, double* lm_cov, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");

@@ -140,7 +140,8 @@ extern "C" int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx
         hipFree(A);
         return sfail(VBA_EHIP, "dynamics factor: hipMemset / upload failed");
     }
-    // the scratch of the queries was sized for 6 n: they refuse this handle from now on, so it goes
+    // the scratch of the queries was sized for 6 n, so it goes: the three queries refuse this handle from now on, and
+    // vba_schur_covariance_dyn allocates it anew for 9 n
     schur_scratch_release(h->rel.sc);
     h->rel = SchurRel{};
     schur_scratch_release(h->q.sc);

@@ -244,6 +244,35 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_covariance_ms(self.h, byref(v)))
         return v.value
 
+    def state_covariance(self, lamda=0.0, pairs=False, strict=True):
+        """``vba_schur_covariance_dyn`` at the resident state of a handle with the dynamics factor (``include/vinsat_ba.h``):
+        blocks of the inverse of the system an ``iterate(lamda)`` would build there.  Returns a dict: ``state [n,9,9]`` -- every
+        pose's marginal, coordinates ``[dp (km), dtheta, dv (km/s)]`` as ``vba_covariance`` orders them -- ``edges [n-1,9,9]`` =
+        ``Sigma(x_i, x_{i+1})`` (rows of pose ``i``, columns of pose ``i + 1``), ``landmark [L,3,3]`` in the caller's landmark
+        order, ``info``, and with ``pairs`` also ``pairs = (blk_i, blk_j, [nblk,6,6])`` as :meth:`covariance` returns them.  Up to
+        the variance factor of the weights.  Nothing on the handle changes: state, step, factor, the dynamics arrays of the last
+        iterate and the bits of the following iterates.
+
+        ``strict`` as in :meth:`covariance`: a system that is not positive definite raises ``VbaError`` naming the row
+        (``info - 1``), or gives NaN everywhere.  A handle without the dynamics factor raises: :meth:`covariance` is its query."""
+        state, edges, lm = np.empty((self.n, 9, 9)), np.empty((max(self.n - 1, 0), 9, 9)), np.empty((self.L, 3, 3))
+        blocks = np.empty((self.structure["blk_i"].size, 6, 6)) if pairs else None
+        info = c_int()
+        self._check(self.lib.vba_schur_covariance_dyn(self.h, float(lamda), state.ctypes.data_as(PD), edges.ctypes.data_as(PD),
+                                                      blocks.ctypes.data_as(PD) if pairs else None, lm.ctypes.data_as(PD), byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur state covariance: the reduced system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        out = dict(state=state, edges=edges, landmark=lm, info=info.value)
+        if pairs:
+            out["pairs"] = (self.structure["blk_i"].copy(), self.structure["blk_j"].copy(), blocks)
+        return out
+
+    def last_state_covariance_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_covariance_dyn_ms(self.h, byref(v)))
+        return v.value
+
     def reliability(self, lamda=0.0, strict=True):
         """``vba_schur_reliability`` at the resident state (``include/vinsat_ba.h``): which row, and which catalogue position,
         the window contradicts.  Returns a dict: ``leverage [m]`` (trace of the row's 2x2 block of the hat matrix, poses AND
@@ -418,6 +447,13 @@ def pose_sigmas(cov):
     attitude [..., 3] rad)``.  The step's ``dtheta`` linearises a rotation of angle ``2 dtheta``: attitude = ``2 sqrt(.)``."""
     d = np.diagonal(_blocks(cov, "pose"), axis1=-2, axis2=-1)
     return np.sqrt(d[..., 0:3]), 2.0 * np.sqrt(d[..., 3:6])
+
+
+def state_sigmas(cov):
+    """1-sigma per pose from :meth:`SchurBA.state_covariance` (its dict, or ``[..., 9, 9]`` blocks): ``(position [..., 3] km,
+    attitude [..., 3] rad, velocity [..., 3] km/s)``.  Attitude is ``2 sqrt(.)`` as in :func:`pose_sigmas`."""
+    d = np.diagonal(_blocks(cov, "state"), axis1=-2, axis2=-1)
+    return np.sqrt(d[..., 0:3]), 2.0 * np.sqrt(d[..., 3:6]), np.sqrt(d[..., 6:9])
 
 
 def landmark_sigmas(cov):
