@@ -63,7 +63,18 @@ enum {
     VBA_DBG_RHS = 9,        /* [n,9]   JTr (BA_filtering.py:48) */
     VBA_DBG_DPOSE = 10,     /* [n,9]   solution of the last LM trial (BA_filtering.py:55) */
     VBA_DBG_SCALARS = 11,   /* [8]     c_obs, w_max, init_residual, last trial residual, lamda32 of last trial, sigma, alpha, n_trials */
-    VBA_DBG_JG = 12         /* [m,2,6] reprojection Jacobian (BA_utils.py:44-48), input order */
+    VBA_DBG_JG = 12,        /* [m,2,6] reprojection Jacobian (BA_utils.py:44-48), input order */
+    /* What the trial kernel of the last call left behind for the NEXT call, as that call will read it (read-only; VBA_ESTATE when
+       the call carried nothing: key carry off, or the states replaced behind it): */
+    VBA_DBG_NEXT_KEYS = 13,     /* [m,2]   carried keys |uv - est| at the trial states, input order */
+    VBA_DBG_NEXT_HIST = 14,     /* [4 + bins] kind (1 exponent digit: 1024 bins, 2 warm: 2048 bins), warm_lo (raw 64 bits), warm shift,
+                                   sel_rank[0], then the digit-0 histogram of the next call's parity */
+    VBA_DBG_NEXT_BUCKETS = 15,  /* [1 + 2048 cap] cap, then the bin buckets of that parity, bin-major (VBA_ESTATE on handles without
+                                   buckets and behind an exponent histogram) */
+    VBA_DBG_PART_TRIAL = 16,    /* [8 + trial_stride] observation blocks, pose-chain blocks, long-edge slots, FUSED, TILES, EMIT,
+                                   split launches (PART 1 + 2), bucket cap in use (0: none); then the block sums of the last trial:
+                                   observation tiles, pose-chain blocks, long edges, unused slots */
+    VBA_DBG_PART_NEXT = 17      /* [observation blocks] block sums of |r| at the trial states (carried with the keys) */
 };
 
 /* library / device */

@@ -234,7 +234,10 @@ def test_debug_fetch_sizes_and_refusals(eng8, win8):
     eng8.set_states(win8["st"], 1e-3)
     eng8.step(12, False)
     sizes = dict(est=2 * m, weight=m, Jg=12 * m, H=36 * n, b=6 * n, Phi=36 * n, r_pred=7 * (n - 1), qgrad=3 * n, Hq=27 * n,
-                 bands=243 * n, rhs=9 * n, dpose=9 * n, scalars=8)
+                 bands=243 * n, rhs=9 * n, dpose=9 * n, scalars=8,
+                 # what the trial left for the next call: 2 observation tiles, 1 pose-chain block, 64 slots of long edges behind a
+                 # header of 8; a warm histogram behind a header of 4; 2048 buckets of 256 keys behind their capacity
+                 next_keys=2 * m, next_hist=4 + 2048, next_buckets=1 + 2048 * 256, part_trial=8 + 2 + 1 + 64, part_next=2)
     assert sorted(sizes) == sorted(DBG)
     for name, size in sizes.items():
         assert _fetch(eng8, DBG[name], size - 1)[0] == EINVAL, name
@@ -242,6 +245,43 @@ def test_debug_fetch_sizes_and_refusals(eng8, win8):
         assert _fetch(eng8, DBG[name], size) == (0, size), name
     assert _fetch(eng8, 99, 4096)[0] == EINVAL
     assert b"unknown debug selector" in eng8.lib.vba_last_error()
+
+
+def test_debug_fetch_refuses_what_was_not_carried(win8):
+    """The selectors of what a trial leaves for the next call: refused with VBA_ESTATE and a message on a handle without bin buckets,
+    behind a call that emitted nothing or an exponent histogram, and once the states were replaced; part_trial is always there."""
+    big = 1 + 2048 * 256
+    carried = ("next_keys", "next_hist", "next_buckets", "part_next")
+
+    def stepped(mode=-1, **options):
+        e = BAEngine(8, 300, mode=mode)
+        _upload(e, win8)
+        for k, v in options.items():
+            getattr(e, f"set_{k}")(v)
+        e.set_states(win8["st"], 1e-3)
+        e.step(12, False)
+        return e
+
+    e = stepped(mode=0)                             # bandwidth mode: keys and a warm histogram, no buckets
+    assert _fetch(e, DBG["next_buckets"], big)[0] == ESTATE and b"no bin buckets" in e.lib.vba_last_error()
+    for name in ("next_keys", "next_hist", "part_next", "part_trial"):
+        assert _fetch(e, DBG[name], big)[0] == 0, name
+    e.close()
+    e = stepped(key_carry=False)                    # nothing emitted
+    for name in carried:
+        assert _fetch(e, DBG[name], big)[0] == ESTATE and b"carried nothing" in e.lib.vba_last_error(), name
+    assert _fetch(e, DBG["part_trial"], big)[0] == 0
+    e.close()
+    e = stepped(warm_select=False)                  # the exponent histogram: 1024 bins, no buckets behind it
+    assert _fetch(e, DBG["next_hist"], big) == (0, 4 + 1024)
+    assert _fetch(e, DBG["next_buckets"], big)[0] == ESTATE and b"exponent histogram" in e.lib.vba_last_error()
+    e.close()
+    e = stepped()
+    assert _fetch(e, DBG["next_keys"], big)[0] == 0
+    e.set_states(win8["st"], 1e-3)                  # the keys on the device belong to states that are gone
+    for name in carried:
+        assert _fetch(e, DBG[name], big)[0] == ESTATE and b"carried nothing" in e.lib.vba_last_error(), name
+    e.close()
 
 
 def test_debug_fetch_refuses_after_a_pipelined_call(eng8, win8):

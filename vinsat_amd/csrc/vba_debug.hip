@@ -49,6 +49,49 @@ int fetch_rows(vba_handle h, const DevView& V, int window, int what, const Debug
     for (int64_t s = 0; s < m; ++s) std::memcpy(o.out + perm[s] * per, tmp.data() + s * per, per * 8);
     return VBA_OK;
 }
+
+// VBA_DBG_NEXT_*: what the trial kernel of the last call left for the next one (k_trial EMIT), as that call will read it -- the slots
+// of the parity V.par ^ 1.  Read-only.  A call that emitted nothing (key carry off), or whose carried data the host has dropped since
+// (vba_set_states, an abandoned call), has nothing to show.
+int fetch_next(vba_handle h, const DevView& V, const WinScalars& sc, int window, int what, const DebugOut& o) {
+    const int kind = h->carry_enabled ? h->carry_ok : 0;
+    if (!kind)
+        return fail(VBA_ESTATE, "the last call carried nothing into the next one (key carry is off, or the states were replaced behind it)");
+    const int64_t m = h->m[window];
+    const int np = V.par ^ 1;       // parity of the call that reads
+    switch (what) {
+        case VBA_DBG_NEXT_KEYS: {
+            if (int rc = o.room(2 * m)) return rc;
+            std::vector<double> tmp((size_t)m * 2);
+            HIPCHK(hipMemcpy(tmp.data(), V.absr + 2 * (size_t)window * V.m_max, (size_t)m * 16, hipMemcpyDeviceToHost));
+            const std::vector<int64_t>& perm = h->perm[window];
+            for (int64_t s = 0; s < m; ++s) std::memcpy(o.out + perm[s] * 2, tmp.data() + s * 2, 16);
+            return VBA_OK;
+        }
+        case VBA_DBG_NEXT_HIST: {
+            const int bins = kind == 2 ? kSelBins : 1024;
+            if (int rc = o.room(4 + bins)) return rc;
+            std::vector<unsigned> hist(bins);
+            HIPCHK(hipMemcpy(hist.data(), V.hist + (size_t)window * kHistStride + (size_t)np * kSelBins, (size_t)bins * 4, hipMemcpyDeviceToHost));
+            o.out[0] = kind;
+            std::memcpy(o.out + 1, &sc.warm_lo[np], 8);      // (raw bits)
+            o.out[2] = V.warm_shift;
+            o.out[3] = (double)sc.sel_rank[0];
+            for (int b = 0; b < bins; ++b) o.out[4 + b] = hist[b];
+            return VBA_OK;
+        }
+        case VBA_DBG_NEXT_BUCKETS: {
+            if (!V.wbucket) return fail(VBA_ESTATE, "this handle has no bin buckets (it runs the bandwidth-mode kernels)");
+            if (kind != 2) return fail(VBA_ESTATE, "the last call left the exponent histogram: only a warm histogram comes with bin buckets");
+            const int64_t cnt = (int64_t)kSelBins * V.bucket_cap;
+            if (int rc = o.room(1 + cnt)) return rc;
+            o.out[0] = V.bucket_cap;
+            HIPCHK(hipMemcpy(o.out + 1, V.wbucket + ((size_t)window * 2 + np) * kSelBins * (size_t)V.bucket_cap, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+            return VBA_OK;
+        }
+        default: return o.copy(V.part_next + (size_t)window * V.nblk_obs, V.nblk_obs);
+    }
+}
 }  // namespace
 
 int vba_debug_fetch(vba_handle h, int window, int what, double* out, int64_t capacity, int64_t* count) {
@@ -170,6 +213,21 @@ int vba_debug_fetch(vba_handle h, int window, int what, double* out, int64_t cap
             fill_params(p, h->last_iter, h->last_init);
             out[0] = sc.c_obs; out[1] = wmax; out[2] = sc.init_residual; out[3] = sc.trial_residual;
             out[4] = sc.lam32; out[5] = p.sigma; out[6] = p.alpha; out[7] = (double)sc.n_trials;
+            return VBA_OK;
+        }
+        case VBA_DBG_NEXT_KEYS:
+        case VBA_DBG_NEXT_HIST:
+        case VBA_DBG_NEXT_BUCKETS:
+        case VBA_DBG_PART_NEXT: return fetch_next(h, V, sc, window, what, o);
+        case VBA_DBG_PART_TRIAL: {
+            // the block sums of the last trial behind the geometry they were written in (launch_trial_emit reads the same fields)
+            if (int rc = o.room(8 + (int64_t)V.trial_stride)) return rc;
+            const bool split = V.fused_trial == 0 && !V.lat && !V.wbucket;
+            const int emit = h->carry_enabled ? h->carry_ok : 0;
+            out[0] = V.nblk_obs; out[1] = V.nblk_dyn; out[2] = h->last_init ? 0 : V.nblk_long; out[3] = V.fused_trial;
+            out[4] = (V.fused_trial == 0 && !split && emit == 2) ? V.trial_tiles : 1; out[5] = emit; out[6] = split ? 1 : 0;
+            out[7] = V.wbucket ? V.bucket_cap : 0;
+            HIPCHK(hipMemcpy(out + 8, V.part_trial + (size_t)window * V.trial_stride, (size_t)V.trial_stride * 8, hipMemcpyDeviceToHost));
             return VBA_OK;
         }
         default: return fail(VBA_EINVAL, "unknown debug selector");

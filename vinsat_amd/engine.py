@@ -9,7 +9,8 @@ import numpy as np
 from . import _lib
 from ._lib import PD, PI64
 
-DBG = dict(est=0, weight=1, H=2, b=3, Phi=4, r_pred=5, qgrad=6, Hq=7, bands=8, rhs=9, dpose=10, scalars=11, Jg=12)
+DBG = dict(est=0, weight=1, H=2, b=3, Phi=4, r_pred=5, qgrad=6, Hq=7, bands=8, rhs=9, dpose=10, scalars=11, Jg=12,
+           next_keys=13, next_hist=14, next_buckets=15, part_trial=16, part_next=17)
 
 
 def _f64(a):
@@ -391,6 +392,36 @@ class BAEngine:
 
     def last_snoop_ms(self):
         return self._last_ms("snoop")
+
+    def _fetch(self, what, size, window=0):
+        out = np.empty(int(size))
+        cnt = c_int64()
+        _lib.check(self.lib.vba_debug_fetch(self.h, window, DBG[what], _p(out), out.size, byref(cnt)), self.lib)
+        return out[:cnt.value]
+
+    def debug_next(self, window=0):
+        """What the last call's trial kernel left for the next call (``VBA_DBG_NEXT_*``, ``VBA_DBG_PART_NEXT``): dict with ``keys``
+        [m, 2] in input order, ``kind`` (1 exponent digit / 2 warm bins), ``warm_lo`` (bit pattern), ``shift``, ``sel_rank``, ``hist``
+        (uint64 counts), ``part_next`` and -- on handles with bin buckets behind a warm histogram -- ``cap``, ``buckets`` [2048, cap]."""
+        m = self.m[window]
+        hd = self._fetch("next_hist", 4 + 2048, window)
+        d = dict(keys=self._fetch("next_keys", 2 * m, window).reshape(m, 2), kind=int(hd[0]), warm_lo=int(hd[1:2].view(np.uint64)[0]),
+                 shift=int(hd[2]), sel_rank=int(hd[3]), hist=hd[4:].astype(np.uint64),
+                 part_next=self._fetch("part_next", -(-self.m_max // 256), window))
+        geo = self.debug_trial(window)
+        if geo["cap"] and d["kind"] == 2:
+            b = self._fetch("next_buckets", 1 + 2048 * geo["cap"], window)
+            d["cap"], d["buckets"] = int(b[0]), b[1:].reshape(2048, int(b[0]))
+        return d
+
+    def debug_trial(self, window=0):
+        """``VBA_DBG_PART_TRIAL``: the geometry the last trial's block sums were written in and the sums: dict with ``nblk_obs``,
+        ``nblk_dyn``, ``nblk_long``, ``fused``, ``tiles``, ``emit``, ``split``, ``cap`` and ``part_trial`` [trial_stride]."""
+        stride = -(-self.m_max // 256) + max(-(-self.n_max // 256), (self.n_max + 13) // 15) + 64
+        o = self._fetch("part_trial", 8 + stride, window)
+        d = dict(zip(("nblk_obs", "nblk_dyn", "nblk_long", "fused", "tiles", "emit", "split", "cap"), (int(v) for v in o[:8])))
+        d["part_trial"] = o[8:].copy()
+        return d
 
     def debug(self, what, window=0):
         n, m = self.n[window], self.m[window]
