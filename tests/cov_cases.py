@@ -1,7 +1,7 @@
 """The cases of the covariance path tests (tests/test_cov_reference_host.py, tests/test_gpu_covariance_paths.py): synthetic windows
 from the generator of the solve-path tests, pose counts chosen for their position relative to a chunk.
 
-Pose counts per chunk size s -- the smallest that reach each branch of k_cov_chunk / k_cov_sep / k_cov_fix (csrc/vba_cov.hip), with
+Pose counts per chunk size s -- the smallest that reach each branch of k_cov_chunk / k_cov_sep / k_cov_fix (csrc/vba_cov.hip, csrc/vba_cov_walk.h), with
 P = ceil(n / s) chunks, P - 1 separators, the last chunk holding n - (P - 1) s poses:
 
   P = 1 (n <= s: no separator, k_cov_sep returns at once, k_cov_fix adds a zero correction)      s=2: 2;  3: 3;  5: 4, 5;  8: 8

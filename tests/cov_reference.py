@@ -262,7 +262,7 @@ ZERO_PIVOT, INDEFINITE = 4, 8
 
 
 def recurrence_flags(bands, lam32=0.0):
-    """The pivot checks of the device's forward sweep (cov_walk) on the fp64 block recurrence without row exchanges: ZERO_PIVOT
+    """The pivot checks of the device's forward sweep (cov_pivots, csrc/vba_cov_walk.h) on the fp64 block recurrence without row exchanges: ZERO_PIVOT
     if a pivot is not above 1e-10 of the diagonal entry it started from, INDEFINITE if one is negative."""
     Ad, B = sym_blocks(bands, lam32)
     n = Ad.shape[0]

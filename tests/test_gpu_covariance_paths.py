@@ -1,5 +1,5 @@
 """Both paths of the covariance query (csrc/vba_cov.hip: the sequential walk k_cov_seq and the partitioned k_cov_chunk / k_cov_sep /
-k_cov_fix), per component, against the system the query inverted.
+k_cov_fix; both run the one recurrence of csrc/vba_cov_walk.h), per component, against the system the query inverted.
 
 Every case (tests/cov_cases.py): pipeline off, upload, states at the initial guess with lamda 1e-4, vba_step(9, landmark-only),
 vba_step(10, full), then vba_covariance(14, damped, with the super-diagonal) undamped and damped, then vba_step(14, full) and its
@@ -22,7 +22,7 @@ Largest measured device / CPU ratios on the MI355X (figure / max(CPU figure of t
   test_partitioned        1.72 (chunk 3, n = 4, tight handle, undamped, super pos-pos pose 1); tight and loose handles alike
   test_batches            3.22 (chunks of 2, latency kernels, the two-pose window, damped, super vel-att); 2.33 with chunks of 5
 
-No case exposed a fault in csrc/vba_cov.hip.
+No case exposed a fault in csrc/vba_cov.hip or csrc/vba_cov_walk.h.
 """
 import numpy as np
 import pytest

@@ -9,7 +9,8 @@
 //   vba_schedule.hip     vba_run_schedule (chained calls), the graph cache that replays its first pass, the chain profile
 //   vba_iterate.hip      vba_iterate* (states over PCIe, the pipelined driver loop, host watch)
 //   vba_sharded_api.hip  observation-sharded mode (vba_sh_*)
-//   vba_cov.hip          per-pose marginal covariances (vba_covariance); the step and the scaffold the three queries share
+//   vba_query.hip        the scaffold of the queries at the resident states: checks, scratch, timing, the shadow front they share
+//   vba_cov.hip          per-pose marginal covariances (vba_covariance): the selected inversion behind that front
 //   vba_rel.hip          per-row leverages and w-tests (vba_reliability)
 //   vba_power.hip        per-row detectable biases and influences, the fit's variance factor (vba_outlier_power)
 //   vba_snoop.hip        data snooping: rows rejected by their w-test on the device (vba_snoop, vba_snoop_scaled)
@@ -216,7 +217,7 @@ struct vba_context {
     int warm_misses = 0;                    // number of calls whose warm select missed and was repeated with the exact digits (diagnostic)
     double* d_dbg = nullptr;                // lazily allocated scratch for debug fetch
     size_t dbg_cap = 0;
-    // The uncertainty queries (vba_cov.hip, vba_rel.hip, vba_power.hip): each has a scratch allocated by its first call, and the
+    // The uncertainty queries (vba_query.hip; vba_cov.hip, vba_rel.hip, vba_power.hip): each has a scratch allocated by its first call, and the
     // time of its last call from cov_ev0, recorded in front of the covariance step all three start with
     QueryScratch q_cov;                      // the shadow of every array the front of a call writes, Sigma's blocks (cov_layout)
     QueryScratch q_rel;                      // rel_layout: the two row arrays, the device copy of perm, the pose summary
@@ -330,8 +331,8 @@ int vba_set_chain_profile(vba_handle h, int on);
 void watch_stop(vba_handle h);
 void watch_quiesce(vba_handle h);
 
-// ---- vba_cov.hip
-// The step the three queries share: the shadow front of a full-phase call and the selected inversion, into the scratch of the
+// ---- vba_query.hip
+// The step the queries share: the shadow front of a full-phase call and the selected inversion, into the scratch of the
 // covariance query (see vba_cov.hip).
 struct CovQuery {
     DevView V;                  // the shadow view: wraw, sc (maximum raw weight of parity V.par) and states are what the row pass reads
@@ -344,17 +345,30 @@ int cov_build_invert(vba_handle h, int iter, int damped, CovQuery& q);
 // The scaffold of a query around that step.  query_reserve: q.d holds at least `bytes` (the total of the query's layout,
 // vba_query_layout.h), kept or grown; `what` ends the message of a failed allocation.  query_finish: the end event behind the
 // query's last kernel, the wait for it, q.ms since cov_ev0.  query_last_ms: what the vba_last_*_ms getters return.
+// query_copy_out: the copy of a per-window result to the host (`used[w] * per` doubles of every window's `stride`; the rest stays
+// as the caller left it).
 int query_reserve(vba_handle h, QueryScratch& q, size_t bytes, const char* what);
 int query_finish(vba_handle h, QueryScratch& q);
 int query_last_ms(vba_handle h, QueryScratch vba_context::*q, float* ms, const char* none_ran);
+int query_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per);
+
+// ---- vba_cov.hip
+// What of the covariance scratch is not the shadow view's (cov_layout, vba_query.hip), and the selected inversion of the shadow
+// view's bands into it: the launches behind the front, on the path the solver setting selects.
+struct CovBufs {
+    WinScalars* sc;
+    double* pool;
+    double *diag, *sup;         // the two [W][n_max][81] result arrays
+    unsigned* flags;
+    double *X, *contrib, *sepb, *SSd, *SSs;     // partitioned path: X, chunk contributions, separator bands, separator blocks of Sigma
+};
+int launch_cov_invert(vba_handle h, const DevView& V, const CovBufs& b, int damped, hipStream_t s);
 
 // ---- vba_rel.hip
 // What the row passes behind the covariance step share on the host: the device copy of the upload's permutation (sorted position ->
-// input row, [W][m_max], part of the reliability scratch, uploaded for the windows whose rows changed), and the copy of a
-// per-window result to the host (`used[w] * per` doubles of every window's `stride`; the rest stays as the caller left it).
+// input row, [W][m_max], part of the reliability scratch, uploaded for the windows whose rows changed).
 int rel_device_perm(vba_handle h, const int** d_perm);
 int rel_device_bufs(vba_handle h, RelBufs& b);
-int query_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per);
 
 // ---- vba_snoop.hip
 // vba_upload_observations of a window whose handle has snooped: the window's mask is cleared (its rows are new ones)

@@ -2,7 +2,7 @@
 // observation row, and a per-pose summary, at the resident states.
 //
 // Definitions (include/vinsat_ba.h carries the contract).  Sigma is the inverse of the system vba_covariance inverts -- the same
-// shadow front, the same selected inversion, the same damping and symmetrisation rules (vba_cov.hip: cov_build_invert).  For row k
+// shadow front, the same selected inversion, the same damping and symmetrisation rules (vba_query.hip: cov_build_invert).  For row k
 // of pose i = ii[k], with J_k [2,6] the reprojection Jacobian over [dp, dtheta] (VBA_DBG_JG), r_k = uv - est, w_k the final robust
 // weight (w_raw / w_max) conf (VBA_DBG_WEIGHT) and S_i = Sigma_ii[:6, :6]:
 //   P_k      = w_k J_k S_i J_k^T          2x2; only its symmetric part is formed (S_i enters through its upper triangle)
@@ -79,30 +79,6 @@ static int rel_reserve(vba_handle h, RelBufs& b) {
     if (rc) return rc;
     Carver place{static_cast<char*>(h->q_rel.d)};
     b = rel_layout(place, W, N, M);
-    return VBA_OK;
-}
-
-// per-window results: rows beyond a window's count stay as the caller left them
-int query_copy_out(double* out, const double* dev, size_t W, size_t stride, const std::vector<int>& used, size_t per) {
-    bool full = true;
-    for (size_t w = 0; w < W; ++w) full = full && (size_t)used[w] * per == stride;
-    if (full) {
-        HIPCHK(hipMemcpy(out, dev, W * stride * 8, hipMemcpyDeviceToHost));
-        return VBA_OK;
-    }
-    if (W <= 8) {
-        for (size_t w = 0; w < W; ++w)
-            HIPCHK(hipMemcpy(out + w * stride, dev + w * stride, (size_t)used[w] * per * 8, hipMemcpyDeviceToHost));
-        return VBA_OK;
-    }
-    std::vector<double> tmp;        // many ragged windows: one copy, then the used part of every window
-    try {
-        tmp.resize(W * stride);
-    } catch (const std::bad_alloc&) {
-        return fail(VBA_ENOMEM, "host staging for the ragged copy of a reliability output failed");
-    }
-    HIPCHK(hipMemcpy(tmp.data(), dev, W * stride * 8, hipMemcpyDeviceToHost));
-    for (size_t w = 0; w < W; ++w) std::memcpy(out + w * stride, tmp.data() + w * stride, (size_t)used[w] * per * 8);
     return VBA_OK;
 }
 
