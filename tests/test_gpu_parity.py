@@ -527,7 +527,10 @@ def test_sharded_c4_window_on_eight_emulated_ranks_vs_reference_states():
 
 def test_median_with_massive_ties_and_signed_zero():
     """All residuals identical (and a block of exact zeros): the radix select must still return the exact lower
-    median; exercises the compaction-list overflow path of the select."""
+    median.  Most keys share their top 32 bits with the median -- the offset is exactly 3.0, so the projection's rounding of either
+    sign splits them over two prefixes: the device's keys put 1063 of the 1280 in the compacted list -- which is more than is
+    ranked by counting, so digits 3 .. 5 finish the select.  (Not the overflow fallback: a list of an unsharded handle holds
+    2 m_max keys and a window has no more; tests/test_gpu_select_paths.py lists the branches nothing reaches.)"""
     from vinsat_amd.engine import BAEngine
     from vinsat_amd import od_pipe, synth
     det, orb = synth.make_sequence(synth.WindowConfig("ties", 16, 40, 5), seed=2)
@@ -1204,8 +1207,12 @@ def test_warm_select_and_folded_accept_test_give_the_bits_of_the_exact_path(c2, 
 
 
 def test_warm_select_with_long_bins_and_ties():
-    """Keys that pile up in one warm bin (half of all residuals identical): the list is longer than what is ranked by
-    counting and goes through the radix digits of the in-bin offset; the median must still be the exact lower median."""
+    """Half of all residuals identical at the first call's states: the exact select of that call finishes by digits over a long
+    list.  The carried calls behind it run at moved states, where the identical residuals have spread: on the device their warm
+    bins hold 10, 3 and 1 keys, every one of them hits (``warm_select_misses`` stays 0) and is ranked in one sub-bin of a short
+    list.  The median must be the exact lower median on every call, with and without the warm select.  (Long warm bins, the first
+    digit of the in-bin offset and the radix digits behind it: tests/test_gpu_select_paths.py::test_warm_kernel.  The counting
+    branch under kWarmCount is not reached by any list: it needs a warm shift below 8, and 42 .. 51 are accepted.)"""
     from vinsat_amd.engine import BAEngine
     from vinsat_amd import od_pipe, synth
     cfg = synth.WindowConfig("ties", 24, 400, 5)
