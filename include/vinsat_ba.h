@@ -650,8 +650,8 @@ int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t cap
  * (S, g and the factor's arrays are re-sized), lamda goes on the velocity diagonal too, vba_schur_get_state returns the updated
  * velocities, and the build time of vba_schur_last_ms includes the factor's kernels.  vba_schur_reweight, vba_schur_get_weights
  * and vba_schur_median work unchanged; vba_schur_covariance, vba_schur_reliability and vba_schur_snoop return VBA_ESTATE on such a
- * handle (their redundancy counts and gathers assume the 6 n system); vba_schur_covariance_dyn is its covariance query.  A handle
- * that never calls this behaves as before.
+ * handle (their redundancy counts and gathers assume the 6 n system); vba_schur_covariance_dyn, vba_schur_reliability_dyn and
+ * vba_schur_snoop_dyn are its queries.  A handle that never calls this behaves as before.
  * Errors: VBA_EINVAL for n < 2, a gap outside 1 .. 64, a time_idx that does not increase, a sigma_dyn that is not positive and
  * finite; VBA_ESTATE before the upload or on a handle that has the factor already. */
 int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx /*[n]*/, double sigma_dyn);
@@ -766,6 +766,50 @@ int vba_schur_rejected(vba_schur_handle h, unsigned char* row_mask /*[m] or NULL
 int vba_schur_snoop_restore(vba_schur_handle h);
 /* HIP-event time of the last vba_schur_snoop on this handle (the reliability query's device part and the passes of the rule) */
 int vba_schur_last_snoop_ms(vba_schur_handle h, float* ms);
+/* Reliability on a handle with the dynamics factor (vba_schur_enable_dynamics), at the resident state: which observation row and
+ * which catalogue position the window contradicts when the factor ties every pose to its neighbours, and how much redundancy the
+ * fit has.  H = [[B9, E9], [E9^T, C]] is as vba_schur_covariance_dyn(h, lamda, ...) builds it, Sigma = H^-1.
+ *   leverage, wtest, lm_leverage, lm_wtest, lm_stats, pose_stats: word for word as vba_schur_reliability defines them (the NaN
+ *   rules, the w == 0 rule and the closed form of a landmark without rows included), with Sigma_ii, Sigma_il and Sigma_ll blocks
+ *   of THIS Sigma.  Rows do not depend on the velocity and E9 has no velocity rows, so these are the 6x6 blocks out of the pose
+ *   part (top-left 6 n x 6 n) of S9^-1 and the landmark marginals of vba_schur_covariance_dyn.
+ *   Edge i (pose i -> pose i + 1) is a 6-row observation of weight sigma_dyn with J_i = [A_i | -D] (6x12) over
+ *   x = [dp_i, dv_i, dp_{i+1}, dv_{i+1}], A_i = D Phi_i of the query's own build at the resident state; Sigma12 = the components
+ *   {0, 1, 2, 6, 7, 8} of state_cov[i], edge_cov[i] and state_cov[i + 1] of vba_schur_covariance_dyn:
+ *     edge_leverage[i] = tr(sigma_dyn J_i Sigma12 J_i^T) in (0, 6]  (each diagonal entry of J Sigma12 J^T on its own, summed in
+ *                        index order),   edge_omega[i] = sigma_dyn |r_i|^2.
+ *   There is NO w-test of an edge, on purpose.  At the weights of this project (sigma_dyn = 1e4) an edge's leverage lies between
+ *   5.89 and 5.999 of 6, the smallest eigenvalue of I - P_e between -4e-10 and 1e-11: sqrt(sigma_dyn r^T (I - P_e)^-1 r) divides
+ *   by rounding.  Two NumPy routes to it (dense inverse, Schur route) disagree by 2e-3 to 0.7 relative and give NaN on one or
+ *   two edges; the edges carry next to no redundancy (0.18 of 66 on 12 poses / 150 landmarks).  The leverage itself is well
+ *   conditioned (the routes agree to 1.5e-10) and the redundancy of the fit needs it, so it is returned.  Edges are never rejected.
+ *   fit[10] = {Omega = rows, priors and edges: the cost of vba_schur_iterate on this handle, in a summation order of its own;
+ *              m_eff; t_rows; t_prior; rho = 2 m_eff + 3 L + 6 (n - 1) - t_rows - t_prior - t_edges; s0sq = Omega / rho (NaN if
+ *              rho <= 0); largest finite row wtest; largest finite landmark wtest; t_edges = sum edge_leverage;
+ *              Omega_edges = sum edge_omega}: slots 0 .. 7 are those of vba_schur_reliability.  The traces obey
+ *              t_rows + t_prior + t_edges + lamda tr(H^-1) = 9 n + 3 L.
+ * Any output may be NULL, in any combination; what is asked for decides the copies only.  *info, the NaN-everywhere rule and the
+ * error codes are those of vba_schur_covariance_dyn; a handle without the factor gets VBA_ESTATE (vba_schur_reliability is its
+ * query, which keeps refusing a handle that has the factor).  The query changes nothing: state, last_info, last_ms, debug_fetch
+ * 3 .. 6 and last_covariance_dyn_ms read as before, and the following iterates and vba_schur_covariance_dyn queries return the bits
+ * they would have returned without it.  No float atomics, every sum has one order: equal problems give equal bits. */
+int vba_schur_reliability_dyn(vba_schur_handle h, double lamda, double* leverage /*[m] or NULL*/, double* wtest /*[m] or NULL*/,
+                              double* lm_leverage /*[L] or NULL*/, double* lm_wtest /*[L] or NULL*/, double* lm_stats /*[L][3] or NULL*/,
+                              double* pose_stats /*[n][3] or NULL*/, double* edge_leverage /*[n-1] or NULL*/,
+                              double* edge_omega /*[n-1] or NULL*/, double* fit /*[10] or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_reliability_dyn on this handle (the device part of vba_schur_covariance_dyn and the passes) */
+int vba_schur_last_reliability_dyn_ms(vba_schur_handle h, float* ms);
+/* Data snooping on a handle with the dynamics factor: the rule of vba_schur_snoop, steps 1 to 3 as they stand, with the same
+ * counts, crit_used, min_rows and min_track, fed by the device part of vba_schur_reliability_dyn(h, lamda, ...); with scaled it
+ * uses that query's fit[5].  Edges are never rejected.  vba_schur_rejected and vba_schur_snoop_restore serve both snoops.  From the
+ * call's return the handle gives, bit for bit, what a fresh handle gives that has the same structure, the same time_idx and
+ * sigma_dyn, those rows' weights zeroed and the same state (vba_schur_iterate, vba_schur_covariance_dyn,
+ * vba_schur_reliability_dyn).  A call that rejects nothing changes nothing.  Errors: as vba_schur_snoop, and VBA_ESTATE on a
+ * handle without the factor. */
+int vba_schur_snoop_dyn(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts /*[3] or NULL*/,
+                        double* crit_used /*or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_snoop_dyn on this handle */
+int vba_schur_last_snoop_dyn_ms(vba_schur_handle h, float* ms);
 /* Robust re-weighting of the free-landmark fit: the reference's weights (BA_filtering.py:21-25) at the resident state, written
  * into the handle's weight array in place, on the device.  The reference computes them once per BA() call and holds them through
  * its LM trials; here the caller decides when (vinsat_amd/schur.py: solve(robust=...)).

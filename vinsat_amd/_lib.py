@@ -104,6 +104,10 @@ SIGNATURES = {
     "vba_schur_rejected": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
     "vba_schur_snoop_restore": (c_int, [c_void_p]),
     "vba_schur_last_snoop_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_reliability_dyn": (c_int, [c_void_p, c_double, PD, PD, PD, PD, PD, PD, PD, PD, PD, POINTER(c_int)]),
+    "vba_schur_last_reliability_dyn_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_snoop_dyn": (c_int, [c_void_p, c_double, c_double, c_int, c_int, c_int, POINTER(c_int), PD, POINTER(c_int)]),
+    "vba_schur_last_snoop_dyn_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_reweight": (c_int, [c_void_p, c_double, PD, PD, POINTER(c_int)]),
     "vba_schur_get_weights": (c_int, [c_void_p, PD, PD]),
     "vba_schur_last_reweight_ms": (c_int, [c_void_p, POINTER(c_float)]),

@@ -21,8 +21,9 @@
 //   vba_schur_factor.hip  k_potrf64, k_potrf64b, k_gemm_abt, k_syrk_panel and the order of their launches
 //   vba_schur_cov.hip     vba_schur_covariance: k_trinv_step, k_syrk_wtw, k_cov_gather, k_lm_cov; vba_schur_covariance_dyn on top:
 //                         k_syrk_wtw_sel, k_state_gather (index map and tile list: vba_schur_dyn_cov.h)
-//   vba_schur_rel.hip     vba_schur_reliability: k_rel_rows, k_rel_stats, k_rel_totals
-//   vba_schur_snoop.hip   vba_schur_snoop, vba_schur_rejected, vba_schur_snoop_restore and their passes
+//   vba_schur_rel.hip     vba_schur_reliability: k_rel_rows, k_rel_stats, k_rel_totals; vba_schur_reliability_dyn on top:
+//                         k_rel_edges, k_rel_edge_totals (closed form of the edge leverage: vba_schur_dyn_rel.h)
+//   vba_schur_snoop.hip   vba_schur_snoop, vba_schur_snoop_dyn, vba_schur_rejected, vba_schur_snoop_restore and their passes
 //   vba_schur_robust.hip  vba_schur_reweight, vba_schur_get_weights, vba_schur_median and their passes
 //   vba_schur_dyn.hip     vba_schur_enable_dynamics and the kernels of the factor
 //
@@ -47,7 +48,12 @@
 //   k_rel_rows      thread per row: pose-landmark cross-covariance Sigma_il from the gathered blocks and Y, leverage and w-test
 //   k_rel_stats     thread per landmark / per pose: their rows' statistics; the catalogue prior of a landmark as an observation
 //   k_rel_totals    one block: cost, redundancy, variance factor, largest tests (strided partial sums, one tree)
-// Data snooping (vba_schur_snoop: the device part of the reliability query, then the passes of vba_schur_snoop.hip)
+// Reliability of a handle with the dynamics factor (vba_schur_reliability_dyn: the device part of vba_schur_covariance_dyn,
+// k_rel_rows and k_rel_stats as above, then)
+//   k_rel_edges        eight lanes per dynamics edge, six at work: a diagonal entry of J Sigma12 J^T each, the edge's leverage
+//   k_rel_edge_totals  one block behind k_rel_totals: the edges' leverages and cost shares folded into the fit
+// Data snooping (vba_schur_snoop: the device part of the reliability query, then the passes of vba_schur_snoop.hip;
+// vba_schur_snoop_dyn: the same passes behind the device part of vba_schur_reliability_dyn)
 // Robust re-weighting (vba_schur_reweight, vba_schur_median: the passes of vba_schur_robust.hip)
 // Orbit-dynamics factor with velocity unknowns (vba_schur_enable_dynamics: the kernels of vba_schur_dyn.hip; the reduced system
 // becomes [6 n pose | 3 n velocity] unknowns, the build and factor kernels fill and factorise it unchanged)

@@ -170,11 +170,13 @@ struct SchurQuery {
 };
 
 // What vba_schur_reliability needs beyond that, allocated by the first reliability query of a handle: its outputs on the device,
-// the per-row and per-landmark cost terms of the totals, and two timing events of its own.
+// the per-row and per-landmark cost terms of the totals, and two timing events of its own.  fit has the ten slots of
+// vba_schur_reliability_dyn (the plain query fills and copies eight); elev [n - 1], the edge leverages, exists on a handle with the
+// dynamics factor only.
 struct SchurRel {
     SchurScratch sc;
     double *lev = nullptr, *wt = nullptr, *om = nullptr, *lmlev = nullptr, *lmwt = nullptr, *lmom = nullptr, *lm_stats = nullptr,
-           *pose_stats = nullptr, *fit = nullptr;
+           *pose_stats = nullptr, *fit = nullptr, *elev = nullptr;
 };
 
 // State of vba_schur_snoop, allocated by the first snoop of a handle and cleared by vba_schur_upload: the weight a rejected row
@@ -259,10 +261,12 @@ int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, in
 int schur_query_alloc(vba_schur_handle h);
 int schur_query_index(vba_schur_handle h);
 int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad);
+int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad);
 
 // ---- vba_schur_rel.hip
 int schur_rel_alloc(vba_schur_handle h);
 int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad);
+int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad);
 
 // ---- vba_schur_dyn.hip
 // the dynamics arrays of a handle with the factor enabled, at the damping of the view

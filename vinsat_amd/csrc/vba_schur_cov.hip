@@ -320,8 +320,9 @@ int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_
 // The device part of vba_schur_covariance_dyn, as schur_query_device but on a handle with the dynamics factor: the dynamics blocks
 // of the build go through arrays of the scratch (DW), W is needed in full (h->bw = nb - 1: nothing skipped), then the listed tiles
 // of S9^-1 (every tile with VBA_SCHUR_COV_FULL=1), the 9x9 blocks, and k_cov_gather / k_lm_cov as they are: they index by V.Npad
-// and read the top-left 6 n x 6 n only (E9 has no velocity rows, so the landmark formula stands).
-static int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad) {
+// and read the top-left 6 n x 6 n only (E9 has no velocity rows, so the landmark formula stands).  Shared with
+// vba_schur_reliability_dyn (vba_schur_rel.hip), which reads what it leaves resident: Q.state, Q.edge, Q.pair, Q.lm, Q.dyn_A, Q.dyn_ecost.
+int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad) {
     SchurQuery& Q = h->q;
     hipStream_t s = h->stream;
     V = query_view(h, lamda);

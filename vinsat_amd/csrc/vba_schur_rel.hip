@@ -1,8 +1,12 @@
 // vba_schur_rel.hip -- the reliability query of the free-landmark mode (vba_schur_reliability; include/vinsat_ba.h carries the
 // contract): the device part of the covariance query (vba_schur_cov.hip), then leverage and w-test of every row and of every
 // catalogue prior, the statistics per landmark and per pose, the totals of the fit.  Its device part is what vba_schur_snoop starts
-// with.  vba_schur.hip carries the map of the units; the closed forms are vba_schur_rel_math.h.
+// with.  vba_schur_reliability_dyn, the query of a handle with the dynamics factor, follows it: the device part of
+// vba_schur_covariance_dyn, the same passes, then the leverage of every dynamics edge and the edges' share of the fit; its device
+// part is what vba_schur_snoop_dyn starts with.  vba_schur.hip carries the map of the units; the closed forms are
+// vba_schur_rel_math.h and vba_schur_dyn_rel.h.
 #include "vba_schur_context.h"
+#include "vba_schur_dyn_rel.h"
 #include "vba_schur_rel_math.h"
 
 namespace {
@@ -179,6 +183,51 @@ __global__ __launch_bounds__(256) void k_rel_totals(SchurView V, const double* l
     }
 }
 
+// ------------------------------------------------------------------------------------------------ with the dynamics factor
+// vba_schur_reliability_dyn, after the device part of vba_schur_covariance_dyn (state and edge blocks, D Phi of the query's own
+// build resident) and the row and statistics passes above, which run unchanged.
+//
+// Edge leverage, EIGHT LANES PER EDGE, six at work (the shape of k_sdyn_edges): lane c forms diagonal entry c of J Sigma12 J^T
+// (vba_schur_dyn_rel.h: row c of J against the seven columns of Sigma12 it is non-zero at, then against itself; the -D half of J
+// is a constant per lane), the six entries meet in lane 0 of the group, which sums them in lane order.  There are n - 1 edges:
+// the kernel is a chain of dependent loads and fma, not a bandwidth matter.
+constexpr int kEdgeLanes = 8;
+
+__global__ __launch_bounds__(256) void k_rel_edges(int n, double sigma, const double* A, const double* state, const double* edge, double* elev) {
+    const int gid = blockIdx.x * 256 + threadIdx.x;
+    const int e = gid / kEdgeLanes, c = gid % kEdgeLanes;
+    double d = 0.0;
+    if (e < n - 1 && c < 6)
+        d = schur_dyn_rel_edge_diag(A + (size_t)e * 36, state + (size_t)e * 81, edge + (size_t)e * 81, state + (size_t)(e + 1) * 81, c);
+    double diag[6];             // (every lane of the wave takes part in the exchange; the lanes past the edges carry zeros)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) diag[k] = __shfl(d, k, kEdgeLanes);
+    if (e < n - 1 && c == 0) elev[e] = schur_dyn_rel_edge_leverage(sigma, diag);
+}
+
+// Behind k_rel_totals, ONE block: the edges' leverages and cost shares summed as k_rel_totals sums the rows (thread t takes the
+// edges t, t + 256, ..., then the tree), folded into the fit k_rel_totals left: Omega and the redundancy gain the edges, s0sq
+// follows, fit[8] = t_edges, fit[9] = Omega_edges.
+__global__ __launch_bounds__(256) void k_rel_edge_totals(int n, int L, const double* elev, const double* eom, double* fit) {
+    __shared__ double red[2][256];
+    const int t = threadIdx.x;
+    double a0 = 0.0, a1 = 0.0;
+    for (int e = t; e < n - 1; e += 256) { a0 += elev[e]; a1 += eom[e]; }
+    red[0][t] = a0; red[1][t] = a1;
+    for (int o = 128; o > 0; o >>= 1) {
+        __syncthreads();
+        if (t < o) { red[0][t] += red[0][t + o]; red[1][t] += red[1][t + o]; }
+    }
+    if (t == 0) {
+        const double tedges = red[0][0], omedges = red[1][0];
+        const double Omega = fit[0] + omedges, meff = fit[1], trows = fit[2], tprior = fit[3];
+        const double rho = ((((2.0 * meff + 3.0 * (double)L) + 6.0 * (double)(n - 1)) - trows) - tprior) - tedges;
+        fit[0] = Omega; fit[4] = rho;
+        fit[5] = rho > 0.0 ? Omega / rho : __builtin_nan("");
+        fit[8] = tedges; fit[9] = omedges;
+    }
+}
+
 }  // namespace
 
 // first reliability query of a handle: its scratch and its two timing events
@@ -189,11 +238,13 @@ int schur_rel_alloc(vba_schur_handle h) {
     const size_t m = (size_t)V.m, L = (size_t)V.L;
     SchurLayout lay;
     const size_t o_lev = lay.need(m * 8), o_wt = lay.need(m * 8), o_om = lay.need(m * 8), o_ll = lay.need(L * 8), o_lw = lay.need(L * 8),
-                 o_lo = lay.need(L * 8), o_ls = lay.need(L * 24), o_ps = lay.need((size_t)V.n * 24), o_fit = lay.need(64);
+                 o_lo = lay.need(L * 8), o_ls = lay.need(L * 24), o_ps = lay.need((size_t)V.n * 24), o_fit = lay.need(80),
+                 o_el = lay.need(h->dyn.enabled ? ((size_t)V.n - 1) * 8 : 0);
     if (int rc = schur_scratch_alloc(R.sc, lay.bytes, "reliability scratch")) return rc;
     char* A = R.sc.arena;
     R.lev = (double*)(A + o_lev); R.wt = (double*)(A + o_wt); R.om = (double*)(A + o_om); R.lmlev = (double*)(A + o_ll); R.lmwt = (double*)(A + o_lw);
     R.lmom = (double*)(A + o_lo); R.lm_stats = (double*)(A + o_ls); R.pose_stats = (double*)(A + o_ps); R.fit = (double*)(A + o_fit);
+    if (h->dyn.enabled) R.elev = (double*)(A + o_el);
     return VBA_OK;
 }
 
@@ -214,7 +265,63 @@ int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, Schu
     return VBA_OK;
 }
 
+// The device part of vba_schur_reliability_dyn, shared with vba_schur_snoop_dyn: schur_query_device_dyn with the landmark marginals
+// from ev_begin on, and unless the factorisation failed the row and statistics passes as the plain query runs them, the edge pass,
+// the totals of the plain query and the edges folded into them.  The edges' cost shares are the ecost of the query's own build.
+int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad) {
+    SchurQuery& Q = h->q;
+    SchurRel& R = h->rel;
+    hipStream_t s = h->stream;
+    if (int rc = schur_query_device_dyn(h, lamda, true, ev_begin, V, bad)) return rc;
+    if (*bad != 0) return VBA_OK;
+    hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
+    hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
+                       R.pose_stats);
+    hipLaunchKernelGGL(k_rel_edges, dim3(((V.n - 1) * kEdgeLanes + 255) / 256), dim3(256), 0, s, V.n, h->dyn.sigma, Q.dyn_A, Q.state, Q.edge, R.elev);
+    hipLaunchKernelGGL(k_rel_totals, dim3(1), dim3(256), 0, s, V, R.lev, R.wt, R.om, R.lmlev, R.lmwt, R.lmom, R.fit);
+    hipLaunchKernelGGL(k_rel_edge_totals, dim3(1), dim3(256), 0, s, V.n, V.L, R.elev, Q.dyn_ecost, R.fit);
+    return VBA_OK;
+}
+
 extern "C" {
+
+int vba_schur_reliability_dyn(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
+                              double* lm_stats, double* pose_stats, double* edge_leverage, double* edge_omega, double* fit, int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    if (!h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    if (int rc = schur_query_index(h)) return rc;
+    if (int rc = schur_rel_alloc(h)) return rc;
+    SchurRel& R = h->rel;
+    hipStream_t s = h->stream;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_rel_device_dyn(h, lamda, R.sc.ev[0], V, &bad)) return rc;
+    *info = bad;
+    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
+    struct Out { double* host; const double* dev; size_t count; };
+    const Out outs[9] = {{leverage, R.lev, m}, {wtest, R.wt, m}, {lm_leverage, R.lmlev, L}, {lm_wtest, R.lmwt, L}, {lm_stats, R.lm_stats, 3 * L},
+                         {pose_stats, R.pose_stats, 3 * n}, {edge_leverage, R.elev, n - 1}, {edge_omega, h->q.dyn_ecost, n - 1}, {fit, R.fit, 10}};
+    if (bad != 0) {                 // no factor, no covariance, no test: NaN, and the row in *info
+        if (int rc = schur_scratch_finish(R.sc, s)) return rc;
+        for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
+        return VBA_OK;
+    }
+    return schur_scratch_finish(R.sc, s, [&]() -> int {
+        SCHK(hipGetLastError());
+        for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
+        return VBA_OK;
+    });
+}
+
+int vba_schur_last_reliability_dyn_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->rel.sc.ms;
+    return VBA_OK;
+}
 
 int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
                           double* lm_stats, double* pose_stats, double* fit, int* info) {

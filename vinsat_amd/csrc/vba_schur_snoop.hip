@@ -1,6 +1,7 @@
-// vba_schur_snoop.hip -- free-landmark data snooping (vba_schur_snoop, vba_schur_rejected, vba_schur_snoop_restore;
+// vba_schur_snoop.hip -- free-landmark data snooping (vba_schur_snoop, vba_schur_snoop_dyn, vba_schur_rejected, vba_schur_snoop_restore;
 // include/vinsat_ba.h carries the contract, vba_schur_context.h the handle, vba_schur.hip the map of the units): its passes, then the
-// entry points.  The passes run behind the device part of vba_schur_reliability on the handle's
+// entry points.  The passes run behind the device part of vba_schur_reliability (of vba_schur_reliability_dyn on a handle with the
+// dynamics factor: the same passes on the same scratch) on the handle's
 // stream and read what it left: wtest of every row, lm_wtest of every catalogue prior, fit[5] = s0sq.  At most one rejection per
 // group; the rule is vba_schur_snoop_pick.h.
 //
@@ -160,16 +161,15 @@ static SchurSnoopView schur_snoop_view(vba_schur_handle h) {
     return W;
 }
 
-extern "C" {
-
-int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
-                    int* info) {
-    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_snoop") + kDynRefusal);
+// The body of vba_schur_snoop and of vba_schur_snoop_dyn (dyn: the handle has the dynamics factor and the tests come from the device
+// part of vba_schur_reliability_dyn; the passes, the masks and the saved weights are the same -- edges are never rejected).
+static int schur_snoop_call(vba_schur_handle h, bool dyn, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts,
+                            double* crit_used, int* info) {
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!(crit >= 0.0)) return sfail(VBA_EINVAL, "crit must be >= 0 (+inf rejects nothing)");
     if (min_rows < 0 || min_track < 0) return sfail(VBA_EINVAL, "min_rows and min_track must be >= 0");
     if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    if (dyn && !h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
     SCHK(hipSetDevice(h->device));
     if (int rc = schur_query_alloc(h)) return rc;
     if (int rc = schur_query_index(h)) return rc;
@@ -179,7 +179,7 @@ int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, i
     hipStream_t s = h->stream;
     SchurView V;
     int bad = 0;
-    if (int rc = schur_rel_device(h, lamda, Z.sc.ev[0], V, &bad)) return rc;
+    if (int rc = dyn ? schur_rel_device_dyn(h, lamda, Z.sc.ev[0], V, &bad) : schur_rel_device(h, lamda, Z.sc.ev[0], V, &bad)) return rc;
     *info = bad;
     if (counts) counts[0] = counts[1] = counts[2] = 0;
     if (bad != 0) {                 // no factor, no test: nothing is rejected; the critical value of a fit that does not exist
@@ -213,6 +213,27 @@ int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, i
         if (counts) counts[k] = now[k];
     }
     if (crit_used) *crit_used = c;
+    return VBA_OK;
+}
+
+extern "C" {
+
+int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
+                    int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_snoop") + kDynRefusal);
+    return schur_snoop_call(h, false, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
+}
+
+int vba_schur_snoop_dyn(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
+                        int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    return schur_snoop_call(h, true, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
+}
+
+int vba_schur_last_snoop_dyn_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->snoop.sc.ms;
     return VBA_OK;
 }
 

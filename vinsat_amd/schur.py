@@ -25,6 +25,8 @@ from ._lib import PD
 
 # fit[8] of vba_schur_reliability, in its order
 FIT_NAMES = ("omega", "m_eff", "t_rows", "t_prior", "rho", "s0sq", "max_wtest", "max_lm_wtest")
+# fit[10] of vba_schur_reliability_dyn: the same eight, then the edges' share of the traces and of the cost
+FIT_NAMES_DYN = FIT_NAMES + ("t_edges", "omega_edges")
 
 
 def alpha_schedule(it):
@@ -339,6 +341,54 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_snoop_ms(self.h, byref(v)))
         return v.value
 
+    def state_reliability(self, lamda=0.0, strict=True):
+        """``vba_schur_reliability_dyn`` at the resident state of a handle with the dynamics factor (``include/vinsat_ba.h``): the
+        dict of :meth:`reliability` -- rows in the CALLER's order, every leverage and test from the covariance of the system WITH
+        the factor -- plus ``edge_leverage [n-1]`` (trace of the edge's 6x6 block of the hat matrix, in ``(0, 6]``) and
+        ``edge_omega [n-1]`` (``sigma_dyn |r|^2``); ``fit`` is a dict of :data:`FIT_NAMES_DYN`, its ``rho`` and ``omega`` count the
+        edges.  There is no w-test of an edge (the header says why).  :func:`suspects` reads the dict unchanged.  Nothing on the
+        handle changes.
+
+        ``strict`` as in :meth:`state_covariance`.  A handle without the dynamics factor raises: :meth:`reliability` is its query."""
+        ne = max(self.n - 1, 0)
+        out = dict(leverage=np.empty(self.m), wtest=np.empty(self.m), lm_leverage=np.empty(self.L), lm_wtest=np.empty(self.L),
+                   lm_stats=np.empty((self.L, 3)), pose_stats=np.empty((self.n, 3)), edge_leverage=np.empty(ne), edge_omega=np.empty(ne))
+        fit, info = np.empty(len(FIT_NAMES_DYN)), c_int()
+        self._check(self.lib.vba_schur_reliability_dyn(self.h, float(lamda), *[a.ctypes.data_as(PD) for a in out.values()],
+                                                       fit.ctypes.data_as(PD), byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur state reliability: the reduced system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        for key in ("leverage", "wtest"):               # device rows are sorted by landmark: back to the caller's order
+            back = np.empty(self.m)
+            back[self.order] = out[key]
+            out[key] = back
+        out["fit"] = dict(zip(FIT_NAMES_DYN, fit.tolist()))
+        out["info"] = info.value
+        return out
+
+    def last_state_reliability_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_reliability_dyn_ms(self.h, byref(v)))
+        return v.value
+
+    def state_snoop(self, lamda=0.0, crit=3.29, scaled=True, min_rows=6, min_track=3, strict=True):
+        """``vba_schur_snoop_dyn``: :meth:`snoop` on a handle with the dynamics factor -- the same rule, arguments and result, fed
+        by the device part of :meth:`state_reliability`.  Edges are never rejected; :meth:`rejected` and :meth:`restore_rejected`
+        serve both."""
+        counts, used, info = (c_int * 3)(), c_double(), c_int()
+        self._check(self.lib.vba_schur_snoop_dyn(self.h, float(lamda), float(crit), int(bool(scaled)), int(min_rows), int(min_track), counts,
+                                                 byref(used), byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur state snoop: the reduced system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        return dict(rows=counts[0], landmarks=counts[1], rows_via_landmarks=counts[2], crit_used=used.value, info=info.value)
+
+    def last_state_snoop_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_snoop_dyn_ms(self.h, byref(v)))
+        return v.value
+
     def reweight(self, alpha):
         """``vba_schur_reweight`` at the resident state (``include/vinsat_ba.h``): the reference's robust weights
         (``BA_filtering.py:21-25``) times the uploaded weights, written into the handle's weights on the device.  ``alpha`` in
@@ -368,7 +418,7 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_reweight_ms(self.h, byref(v)))
         return v.value
 
-    def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10, snoop=None, robust=None):
+    def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10, snoop=None, robust=None, state_snoop=None):
         """Levenberg-Marquardt driver: damping x10 on a rejected trial, /10 on an accepted one.  Returns the cost history.
 
         ``robust = dict(outer=8, alpha=None)`` (any subset) replaces the single LM loop by the robust loop: for ``it`` in
@@ -380,7 +430,10 @@ class SchurBA:
         ``snoop = dict(crit=, scaled=, min_rows=, min_track=, rounds=8)`` (any subset; ``lamda=`` of the query too, 0 by default):
         after the loop ends, at most ``rounds`` rounds of :meth:`snoop`; a round that rejected something is followed by the LM loop again from the
         resident state, one that rejected nothing ends the rounds.  The history gains one entry per round, ``("snoop", dict of
-        :meth:`snoop`)``."""
+        :meth:`snoop`)``.  ``state_snoop = dict(...)`` is the same with :meth:`state_snoop`, the snoop of a handle with the dynamics
+        factor (``snoop=`` on such a handle raises as :meth:`snoop` does); give one of the two."""
+        if snoop is not None and state_snoop is not None:
+            raise ValueError("snoop and state_snoop are the rounds of two kinds of handle: give one of them")
         if robust is None:
             hist = self._lm_loop(lamda0, max_iters, tol)
         else:
@@ -395,12 +448,13 @@ class SchurBA:
                 if res["status"] != 0:
                     break
                 hist += self._lm_loop(lamda0, max_iters, tol)
-        if snoop is None:
+        if snoop is None and state_snoop is None:
             return hist
-        opts = dict(snoop)
+        opts = dict(snoop if state_snoop is None else state_snoop)
+        one_round = self.snoop if state_snoop is None else self.state_snoop
         rounds = int(opts.pop("rounds", 8))
         for _ in range(rounds):
-            res = self.snoop(**opts)
+            res = one_round(**opts)
             hist.append(("snoop", res))
             if res["rows"] + res["landmarks"] == 0:
                 break
