@@ -810,6 +810,67 @@ int vba_schur_snoop_dyn(vba_schur_handle h, double lamda, double crit, int scale
                         double* crit_used /*or NULL*/, int* info);
 /* HIP-event time of the last vba_schur_snoop_dyn on this handle */
 int vba_schur_last_snoop_dyn_ms(vba_schur_handle h, float* ms);
+/* Outlier power of the free-landmark fit: how large an error in a row, or in a catalogue entry, passes the w-test unnoticed, and how
+ * far such an error moves the orbit, the attitude and the landmark.  H, Sigma = H^-1, A_k, Al_k, r_k, w_k, Sigma_ii, Sigma_il,
+ * Sigma_ll and P_k are those of vba_schur_reliability(h, lamda, ...); rows in the sorted order of the upload.  ncp > 0 and finite
+ * is the non-centrality of the test at the chosen power (17.075 for alpha = 0.001, power 0.8 with two degrees of freedom), crit > 0
+ * the critical value the counts use (+inf counts nothing).
+ *
+ * Row k of pose i and landmark l: J_k = [A_k Al_k] (2x9), Sigma_k = [[Sigma_ii, Sigma_il], [Sigma_il^T, Sigma_ll]], R_k = I - P_k
+ * (symmetric part), B_k = w_k Sigma_k J_k^T (9x2; rows 0..2 B_p, 3..5 B_t, 6..8 B_l).  mu_min(R) is the smaller eigenvalue,
+ * mu_max(M, R) the larger root of det(M - mu R) = 0.
+ *   mdb     [m]  sqrt(ncp / (w_k mu_min(R_k)))                    px: the smallest bias in its worst direction the test detects
+ *   ext_pos [m]  sqrt(ncp / w_k  mu_max(B_p^T B_p, R_k))          km: the largest move of the pose's position by an undetected bias
+ *   ext_att [m]  2 sqrt(ncp / w_k  mu_max(B_t^T B_t, R_k))        rad, the 2 |dtheta| convention of vba_covariance
+ *   ext_lm  [m]  sqrt(ncp / w_k  mu_max(B_l^T B_l, R_k))          km: the same for the row's own landmark
+ *   del_pos [m]  |B_p R_k^-1 r_k|                                 km: the move of the pose's position if the row is deleted
+ *   del_lm  [m]  |B_l R_k^-1 r_k|                                 km: the move of the row's landmark if the row is deleted
+ * Catalogue prior of landmark l as an observation: P_l = Sigma_ll / sigma^2, p_max its largest eigenvalue, q = 1 - p_max,
+ * e_l = X_l - X0_l.
+ *   lm_mdb     [L]  sigma sqrt(ncp / q)                           km: the smallest catalogue error the test detects
+ *   lm_ext     [L]  sigma sqrt(ncp) p_max / sqrt(q)               km: the move of the landmark's own estimate by a catalogue error at
+ *                   that limit.  P_l and I - P_l commute, so mu_max(P_l^T P_l, I - P_l) = p_max^2 / q: the roots are p^2 / (1 - p)
+ *                   over the eigenvalues p of P_l, and p^2 / (1 - p) rises on [0, 1).
+ *   lm_del_pos [L]  the largest finite |Sigma_il[0:3,:] (I - P_l)^-1 e_l| / sigma^2 over the rows of l with w > 0 (km): the move of
+ *                   the worst-hit pose if the prior is taken away.
+ * Summaries: pose_fit[i] = {Omega_i = sum w |r|^2 over the rows of pose i in pose_rows order, the sum of their leverages (the bits of
+ * pose_stats[i][0] of vba_schur_reliability), the largest finite ext_pos of its rows, the count of its rows with wtest > crit};
+ * fit[12] = the fit[8] of vba_schur_reliability with its bits, then {rows with wtest > crit, largest finite ext_pos, landmarks with
+ * lm_wtest > crit, largest finite lm_del_pos}.
+ *
+ * Degenerate input is flagged in the value.  w_k == 0: mdb = +inf, the other five 0.  det R_k <= 0 or mu_min(R_k) <= 0: NaN in all
+ * six.  q <= 0 or not finite: lm_mdb and lm_ext NaN.  det(I - P_l) <= 0: lm_del_pos NaN.  A landmark without rows is tested by
+ * nothing: lm_mdb = +inf, lm_ext = 0, lm_del_pos = 0.  *info != 0 (as vba_schur_reliability): every requested output is NaN and the
+ * call returns VBA_OK.
+ *
+ * Any output may be NULL, in any combination: what is asked for decides the copies only.  The promises are those of
+ * vba_schur_reliability: the query changes nothing, later iterates and queries return the bits they would have returned without it,
+ * no float atomics, every sum in one order, equal problems give equal bits.  Synchronous.  Scratch is allocated by the first query of
+ * a handle.  Errors: VBA_EINVAL for a NaN or negative lamda, an ncp that is not positive and finite, a crit that is not positive, a
+ * null handle or info; VBA_ESTATE as vba_schur_reliability, a handle with the dynamics factor included (vba_schur_outlier_power_dyn
+ * is its query).
+ *
+ * Not provided: an external reliability in VELOCITY on a handle with the dynamics factor needs the velocity-pose tiles of S9^-1 for
+ * every pair of poses that share a landmark, which the selected inverse of vba_schur_covariance_dyn does not form; and there is no
+ * power figure for dynamics edges, for the reason vba_schur_reliability_dyn gives for the edge w-test. */
+int vba_schur_outlier_power(vba_schur_handle h, double lamda, double ncp, double crit, double* mdb /*[m] or NULL*/,
+                            double* ext_pos /*[m] or NULL*/, double* ext_att /*[m] or NULL*/, double* ext_lm /*[m] or NULL*/,
+                            double* del_pos /*[m] or NULL*/, double* del_lm /*[m] or NULL*/, double* lm_mdb /*[L] or NULL*/,
+                            double* lm_ext /*[L] or NULL*/, double* lm_del_pos /*[L] or NULL*/, double* pose_fit /*[n][4] or NULL*/,
+                            double* fit /*[12] or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_outlier_power on this handle (the device part of the reliability query and the passes) */
+int vba_schur_last_outlier_power_ms(vba_schur_handle h, float* ms);
+/* vba_schur_outlier_power on a handle with the dynamics factor: every quantity above with the blocks of the Sigma of
+ * vba_schur_reliability_dyn(h, lamda, ...) -- the same row and prior formulas, the same degenerate rules and promises.  fit[14] =
+ * the fit[10] of vba_schur_reliability_dyn with its bits, edges included, then the four slots above; pose_fit[i][1] has the bits of
+ * that query's pose_stats[i][0].  VBA_ESTATE on a handle without the factor (vba_schur_outlier_power is its query). */
+int vba_schur_outlier_power_dyn(vba_schur_handle h, double lamda, double ncp, double crit, double* mdb /*[m] or NULL*/,
+                                double* ext_pos /*[m] or NULL*/, double* ext_att /*[m] or NULL*/, double* ext_lm /*[m] or NULL*/,
+                                double* del_pos /*[m] or NULL*/, double* del_lm /*[m] or NULL*/, double* lm_mdb /*[L] or NULL*/,
+                                double* lm_ext /*[L] or NULL*/, double* lm_del_pos /*[L] or NULL*/, double* pose_fit /*[n][4] or NULL*/,
+                                double* fit /*[14] or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_outlier_power_dyn on this handle */
+int vba_schur_last_outlier_power_dyn_ms(vba_schur_handle h, float* ms);
 /* Robust re-weighting of the free-landmark fit: the reference's weights (BA_filtering.py:21-25) at the resident state, written
  * into the handle's weight array in place, on the device.  The reference computes them once per BA() call and holds them through
  * its LM trials; here the caller decides when (vinsat_amd/schur.py: solve(robust=...)).

@@ -108,6 +108,10 @@ SIGNATURES = {
     "vba_schur_last_reliability_dyn_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_snoop_dyn": (c_int, [c_void_p, c_double, c_double, c_int, c_int, c_int, POINTER(c_int), PD, POINTER(c_int)]),
     "vba_schur_last_snoop_dyn_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_outlier_power": (c_int, [c_void_p, c_double, c_double, c_double] + [PD] * 11 + [POINTER(c_int)]),
+    "vba_schur_last_outlier_power_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_outlier_power_dyn": (c_int, [c_void_p, c_double, c_double, c_double] + [PD] * 11 + [POINTER(c_int)]),
+    "vba_schur_last_outlier_power_dyn_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_reweight": (c_int, [c_void_p, c_double, PD, PD, POINTER(c_int)]),
     "vba_schur_get_weights": (c_int, [c_void_p, PD, PD]),
     "vba_schur_last_reweight_ms": (c_int, [c_void_p, POINTER(c_float)]),

@@ -23,6 +23,8 @@
 //                         k_syrk_wtw_sel, k_state_gather (index map and tile list: vba_schur_dyn_cov.h)
 //   vba_schur_rel.hip     vba_schur_reliability: k_rel_rows, k_rel_stats, k_rel_totals; vba_schur_reliability_dyn on top:
 //                         k_rel_edges, k_rel_edge_totals (closed form of the edge leverage: vba_schur_dyn_rel.h)
+//   vba_schur_power.hip   vba_schur_outlier_power, vba_schur_outlier_power_dyn: k_pow_rows (in the place of k_rel_rows: one gather per
+//                         row, vba_schur_rowpass.h), k_pow_stats, k_pow_totals (closed forms: vba_power_math.h, vba_schur_power_math.h)
 //   vba_schur_snoop.hip   vba_schur_snoop, vba_schur_snoop_dyn, vba_schur_rejected, vba_schur_snoop_restore and their passes
 //   vba_schur_robust.hip  vba_schur_reweight, vba_schur_get_weights, vba_schur_median and their passes
 //   vba_schur_dyn.hip     vba_schur_enable_dynamics and the kernels of the factor
@@ -52,6 +54,12 @@
 // k_rel_rows and k_rel_stats as above, then)
 //   k_rel_edges        eight lanes per dynamics edge, six at work: a diagonal entry of J Sigma12 J^T each, the edge's leverage
 //   k_rel_edge_totals  one block behind k_rel_totals: the edges' leverages and cost shares folded into the fit
+// Outlier power (vba_schur_outlier_power, vba_schur_outlier_power_dyn: the device part of the reliability query of the handle with
+// k_pow_rows as its row pass, then)
+//   k_pow_rows      thread per row: the gather and P_k of k_rel_rows (lev, wt, om with its bits), then B_k = w Sigma_k J_k^T, detectable
+//                   bias, external reliability in position, attitude and landmark, the row's influence, the pull of the prior
+//   k_pow_stats     thread per landmark: detectable catalogue error, its effect on the landmark, the worst-hit pose; per pose: pose_fit
+//   k_pow_totals    one block: the fit of the reliability query and four slots behind it (the tree of k_rel_totals)
 // Data snooping (vba_schur_snoop: the device part of the reliability query, then the passes of vba_schur_snoop.hip;
 // vba_schur_snoop_dyn: the same passes behind the device part of vba_schur_reliability_dyn)
 // Robust re-weighting (vba_schur_reweight, vba_schur_median: the passes of vba_schur_robust.hip)
@@ -295,7 +303,7 @@ int vba_schur_destroy(vba_schur_handle h) {
     if (h->ev_bulk) hipEventDestroy(h->ev_bulk);
     for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
     if (h->dyn.arena) hipFree(h->dyn.arena);
-    for (SchurScratch* z : {&h->robust.sc, &h->snoop.sc, &h->rel.sc, &h->q.sc}) schur_scratch_release(*z);
+    for (SchurScratch* z : {&h->robust.sc, &h->snoop.sc, &h->pow.sc, &h->rel.sc, &h->q.sc}) schur_scratch_release(*z);
     if (h->arena) hipFree(h->arena);
     delete h;
     return VBA_OK;

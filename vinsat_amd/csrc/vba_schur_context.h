@@ -179,6 +179,15 @@ struct SchurRel {
            *pose_stats = nullptr, *fit = nullptr, *elev = nullptr;
 };
 
+// What vba_schur_outlier_power needs beyond the reliability scratch, allocated by the first power query of a handle: its outputs on
+// the device (six figures per row, three per landmark, pose_fit [n][4], fit with the fourteen slots of vba_schur_outlier_power_dyn),
+// pull [m] = |Sigma_il[0:3,:] z_l| of every row for the landmarks' maxima, and two timing events of its own.
+struct SchurPow {
+    SchurScratch sc;
+    double *mdb = nullptr, *epos = nullptr, *eatt = nullptr, *elm = nullptr, *dpos = nullptr, *dlm = nullptr, *pull = nullptr, *lm_mdb = nullptr,
+           *lm_ext = nullptr, *lm_del = nullptr, *pose_fit = nullptr, *fit = nullptr;
+};
+
 // State of vba_schur_snoop, allocated by the first snoop of a handle and cleared by vba_schur_upload: the weight a rejected row
 // had and a byte per row, a byte per landmark (both cumulative), the per-call decisions of the passes, two timing events.
 struct SchurSnoop {
@@ -237,6 +246,7 @@ struct vba_schur_context {
     int64_t npairs = 0;
     SchurQuery q;               // vba_schur_covariance's scratch (nothing until the first query)
     SchurRel rel;               // vba_schur_reliability's scratch on top of it (nothing until the first reliability query)
+    SchurPow pow;               // vba_schur_outlier_power's scratch on top of both (nothing until the first power query)
     SchurSnoop snoop;           // vba_schur_snoop's state (nothing until the first snoop)
     SchurRobust robust;         // vba_schur_reweight's state (nothing until the first re-weighting)
     SchurDyn dyn;               // vba_schur_enable_dynamics' state (nothing on a handle without the dynamics factor)
@@ -265,8 +275,13 @@ int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEv
 
 // ---- vba_schur_rel.hip
 int schur_rel_alloc(vba_schur_handle h);
-int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad);
-int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad);
+int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
+int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
+
+// ---- vba_schur_power.hip
+// k_pow_rows on the handle's stream in the place of k_rel_rows (the power scratch is allocated): lev, wt, om of the reliability
+// scratch with the bits of k_rel_rows, and the six row figures and the prior pull of vba_schur_outlier_power at this ncp
+void schur_pow_rows_launch(vba_schur_handle h, const SchurView& V, double ncp);
 
 // ---- vba_schur_dyn.hip
 // the dynamics arrays of a handle with the factor enabled, at the damping of the view

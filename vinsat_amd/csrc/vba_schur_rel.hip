@@ -4,10 +4,12 @@
 // with.  vba_schur_reliability_dyn, the query of a handle with the dynamics factor, follows it: the device part of
 // vba_schur_covariance_dyn, the same passes, then the leverage of every dynamics edge and the edges' share of the fit; its device
 // part is what vba_schur_snoop_dyn starts with.  vba_schur.hip carries the map of the units; the closed forms are
-// vba_schur_rel_math.h and vba_schur_dyn_rel.h.
+// vba_schur_rel_math.h and vba_schur_dyn_rel.h; the gather of a row is vba_schur_rowpass.h, shared with the row pass of the outlier
+// power query (vba_schur_power.hip), which takes the place of k_rel_rows in the device part when that query runs it.
 #include "vba_schur_context.h"
 #include "vba_schur_dyn_rel.h"
 #include "vba_schur_rel_math.h"
+#include "vba_schur_rowpass.h"
 
 namespace {
 
@@ -19,7 +21,8 @@ namespace {
 //                                                               k >= k' only: for k' > k the block of (k', k) is read transposed)
 //   P_k = w [A Al] [[Sigma_ii, Sigma_il], [Sigma_il^T, Sigma_ll]] [A Al]^T   (symmetric part), leverage = tr P_k, w-test by
 //   rel_wtest2.  A row costs t products of 6x6 by 6x3 for a track of t rows, so the rows of a landmark together cost the t^2 of
-//   k_lm_cov -- spread over t threads that sit side by side in a wave and read the same Y and the same blocks.
+//   k_lm_cov -- spread over t threads that sit side by side in a wave and read the same Y and the same blocks.  The gather and
+//   P_k are schur_row_blocks (vba_schur_rowpass.h).
 // om[k] = w |r|^2 is kept for the totals.
 __global__ __launch_bounds__(256) void k_rel_rows(SchurView V, const double* pair, const int* lp_ptr, const int* lp_blk, const double* lm,
                                                   double* lev, double* wt, double* om) {
@@ -31,76 +34,10 @@ __global__ __launch_bounds__(256) void k_rel_rows(SchurView V, const double* pai
     row_geometry(V, V.states, V.X, k, q);
     om[k] = w * (q.ru * q.ru + q.rv * q.rv);
     if (w == 0.0) { lev[k] = 0.0; wt[k] = 0.0; return; }
-    const int l = V.row_lm[k], beg = V.lm_ptr[l], end = V.lm_ptr[l + 1], a = k - beg, base = lp_ptr[l];
-    double G[18];                   // sum (S^-1)_{i, pose(k')} Y_k' = -Sigma_il
-#pragma unroll
-    for (int e = 0; e < 18; ++e) G[e] = 0.0;
-    for (int k2 = beg; k2 < end; ++k2) {
-        const int c = k2 - beg;
-        const bool tr = c > a;
-        const int slot = base + (tr ? c * (c + 1) / 2 + a : a * (a + 1) / 2 + c);
-        const double* Sg = pair + (size_t)lp_blk[slot] * 36;
-        const int sp = tr ? 1 : 6, sq = tr ? 6 : 1;    // entry (p, q) of (S^-1)_{i, pose(k')}: Sg[p sp + q sq]
-        double Y2[18];
-#pragma unroll
-        for (int e = 0; e < 18; ++e) Y2[e] = V.Y[(size_t)k2 * 18 + e];
-#pragma unroll
-        for (int p = 0; p < 6; ++p) {
-            double g[6];
-#pragma unroll
-            for (int qq = 0; qq < 6; ++qq) g[qq] = Sg[p * sp + qq * sq];
-#pragma unroll
-            for (int cc = 0; cc < 3; ++cc) {
-                double s = G[3 * p + cc];
-#pragma unroll
-                for (int qq = 0; qq < 6; ++qq) s = fma(g[qq], Y2[3 * qq + cc], s);
-                G[3 * p + cc] = s;
-            }
-        }
-    }
-    double jl[6], jc[12];
-    landmark_jacobian(q, jl);
-    pose_jacobian(q, jl, jc);
-    // A Sigma_ii A^T from the diagonal block of the row's own pair (k, k): stored whole and exactly symmetric
-    const double* Sii = pair + (size_t)lp_blk[base + a * (a + 1) / 2 + a] * 36;
-    double q00 = 0.0, q01 = 0.0, q11 = 0.0;
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-        double tu = 0.0, tv = 0.0;
-#pragma unroll
-        for (int qq = 0; qq < 6; ++qq) { tu = fma(Sii[6 * p + qq], jc[qq], tu); tv = fma(Sii[6 * p + qq], jc[6 + qq], tv); }
-        q00 = fma(jc[p], tu, q00);
-        q01 = fma(jc[p], tv, q01);
-        q11 = fma(jc[6 + p], tv, q11);
-    }
-    // A (-Sigma_il) Al^T: x = A G (2x3), then against the rows of Al
-    double x00 = 0.0, x01 = 0.0, x10 = 0.0, x11 = 0.0;
-#pragma unroll
-    for (int cc = 0; cc < 3; ++cc) {
-        double xu = 0.0, xv = 0.0;
-#pragma unroll
-        for (int p = 0; p < 6; ++p) { xu = fma(jc[p], G[3 * p + cc], xu); xv = fma(jc[6 + p], G[3 * p + cc], xv); }
-        x00 = fma(xu, jl[cc], x00);
-        x01 = fma(xu, jl[3 + cc], x01);
-        x10 = fma(xv, jl[cc], x10);
-        x11 = fma(xv, jl[3 + cc], x11);
-    }
-    // Al Sigma_ll Al^T
-    const double* Sl = lm + (size_t)l * 9;
-    double l00 = 0.0, l01 = 0.0, l11 = 0.0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double yu = fma(Sl[3 * r], jl[0], fma(Sl[3 * r + 1], jl[1], Sl[3 * r + 2] * jl[2]));
-        const double yv = fma(Sl[3 * r], jl[3], fma(Sl[3 * r + 1], jl[4], Sl[3 * r + 2] * jl[5]));
-        l00 = fma(jl[r], yu, l00);
-        l01 = fma(jl[r], yv, l01);
-        l11 = fma(jl[3 + r], yv, l11);
-    }
-    const double p00 = w * ((q00 + l00) - (x00 + x00));
-    const double p01 = w * ((q01 + l01) - (x01 + x10));
-    const double p11 = w * ((q11 + l11) - (x11 + x11));
-    lev[k] = p00 + p11;
-    wt[k] = rel_wtest2(p00, p01, p11, q.ru, q.rv, w);
+    SchurRowBlocks b;
+    schur_row_blocks(V, pair, lp_ptr, lp_blk, lm, k, q, w, b);
+    lev[k] = b.p00 + b.p11;
+    wt[k] = rel_wtest2(b.p00, b.p01, b.p11, q.ru, q.rv, w);
 }
 
 // sum of leverage, largest finite w-test, count of rows with w > 0 over a list of rows in list order (idx == nullptr: beg .. end)
@@ -250,15 +187,17 @@ int schur_rel_alloc(vba_schur_handle h) {
 
 // The device part of vba_schur_reliability, shared with vba_schur_snoop: schur_query_device with the landmark marginals from
 // ev_begin on, and unless the factorisation failed (*bad != 0: nothing more is launched) the three passes into the reliability
-// scratch.  The launches and their order are those vba_schur_reliability has always issued.
-int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad) {
+// scratch.  The launches and their order are those vba_schur_reliability has always issued.  pow_ncp > 0
+// (vba_schur_outlier_power): the row pass is k_pow_rows, which leaves lev, wt, om as k_rel_rows does and that query's row figures.
+int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp) {
     SchurQuery& Q = h->q;
     SchurRel& R = h->rel;
     hipStream_t s = h->stream;
     if (int rc = schur_query_device(h, lamda, true, ev_begin, V, bad)) return rc;
     if (*bad != 0) return VBA_OK;
     // every output is formed whatever is asked for: what is asked for decides the copies only
-    hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
+    if (pow_ncp > 0.0) schur_pow_rows_launch(h, V, pow_ncp);
+    else hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
     hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
                        R.pose_stats);
     hipLaunchKernelGGL(k_rel_totals, dim3(1), dim3(256), 0, s, V, R.lev, R.wt, R.om, R.lmlev, R.lmwt, R.lmom, R.fit);
@@ -268,13 +207,15 @@ int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, Schu
 // The device part of vba_schur_reliability_dyn, shared with vba_schur_snoop_dyn: schur_query_device_dyn with the landmark marginals
 // from ev_begin on, and unless the factorisation failed the row and statistics passes as the plain query runs them, the edge pass,
 // the totals of the plain query and the edges folded into them.  The edges' cost shares are the ecost of the query's own build.
-int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad) {
+// pow_ncp as in schur_rel_device.
+int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp) {
     SchurQuery& Q = h->q;
     SchurRel& R = h->rel;
     hipStream_t s = h->stream;
     if (int rc = schur_query_device_dyn(h, lamda, true, ev_begin, V, bad)) return rc;
     if (*bad != 0) return VBA_OK;
-    hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
+    if (pow_ncp > 0.0) schur_pow_rows_launch(h, V, pow_ncp);
+    else hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
     hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
                        R.pose_stats);
     hipLaunchKernelGGL(k_rel_edges, dim3(((V.n - 1) * kEdgeLanes + 255) / 256), dim3(256), 0, s, V.n, h->dyn.sigma, Q.dyn_A, Q.state, Q.edge, R.elev);

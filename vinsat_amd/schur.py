@@ -27,6 +27,10 @@ from ._lib import PD
 FIT_NAMES = ("omega", "m_eff", "t_rows", "t_prior", "rho", "s0sq", "max_wtest", "max_lm_wtest")
 # fit[10] of vba_schur_reliability_dyn: the same eight, then the edges' share of the traces and of the cost
 FIT_NAMES_DYN = FIT_NAMES + ("t_edges", "omega_edges")
+# the four slots vba_schur_outlier_power(_dyn) puts behind the fit of the reliability query, and its arrays in the order of the entry
+POWER_FIT_NAMES = ("n_rows_over_crit", "max_ext_pos", "n_lm_over_crit", "max_lm_del_pos")
+POWER_ROW_KEYS = ("mdb", "ext_pos", "ext_att", "ext_lm", "del_pos", "del_lm")
+POWER_LM_KEYS = ("lm_mdb", "lm_ext", "lm_del_pos")
 
 
 def alpha_schedule(it):
@@ -389,6 +393,56 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_snoop_dyn_ms(self.h, byref(v)))
         return v.value
 
+    def _outlier_power(self, dyn, lamda, ncp, crit, strict):
+        names = FIT_NAMES_DYN + POWER_FIT_NAMES if dyn else FIT_NAMES + POWER_FIT_NAMES
+        out = {k: np.empty(self.m) for k in POWER_ROW_KEYS}
+        out.update({k: np.empty(self.L) for k in POWER_LM_KEYS})
+        out["pose_fit"] = np.empty((self.n, 4))
+        fit, info = np.empty(len(names)), c_int()
+        entry = self.lib.vba_schur_outlier_power_dyn if dyn else self.lib.vba_schur_outlier_power
+        self._check(entry(self.h, float(lamda), float(ncp), float(crit), *[a.ctypes.data_as(PD) for a in out.values()], fit.ctypes.data_as(PD),
+                          byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur {'state ' if dyn else ''}outlier power: the reduced system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        for key in POWER_ROW_KEYS:                      # device rows are sorted by landmark: back to the caller's order
+            back = np.empty(self.m)
+            back[self.order] = out[key]
+            out[key] = back
+        out["fit"] = dict(zip(names, fit.tolist()))
+        out["info"] = info.value
+        return out
+
+    def outlier_power(self, lamda=0.0, ncp=17.075, crit=3.29, strict=True):
+        """``vba_schur_outlier_power`` at the resident state (``include/vinsat_ba.h`` defines every figure): how large an error in a
+        row or in a catalogue entry passes the w-test of :meth:`reliability` unnoticed, and how far it moves the fit.  Returns a
+        dict: per row, in the CALLER's order, ``mdb [m]`` (px), ``ext_pos`` (km), ``ext_att`` (rad), ``ext_lm`` (km) -- the
+        detectable bias and what an undetected one does to the pose's position, its attitude and the row's landmark -- and
+        ``del_pos``, ``del_lm`` (km), the moves if the row is deleted; per landmark ``lm_mdb [L]``, ``lm_ext``, ``lm_del_pos`` (km):
+        the detectable catalogue error, what it does to the landmark's estimate, and how far the worst-hit pose moves if the prior
+        is taken away; ``pose_fit [n,4]`` = (cost share, sum of leverage, largest finite ``ext_pos``, rows with ``wtest > crit``);
+        ``fit``, a dict of :data:`FIT_NAMES` then :data:`POWER_FIT_NAMES`; ``info``.  ``ncp`` is the non-centrality of the test at
+        the chosen power.  Up to the variance factor of the weights (:func:`scaled_power`).  Nothing on the handle changes.
+
+        ``strict`` as in :meth:`reliability`."""
+        return self._outlier_power(False, lamda, ncp, crit, strict)
+
+    def last_outlier_power_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_outlier_power_ms(self.h, byref(v)))
+        return v.value
+
+    def state_outlier_power(self, lamda=0.0, ncp=17.075, crit=3.29, strict=True):
+        """``vba_schur_outlier_power_dyn``: the dict of :meth:`outlier_power` on a handle with the dynamics factor, every figure from
+        the covariance of the system WITH the factor; ``fit`` is a dict of :data:`FIT_NAMES_DYN` then :data:`POWER_FIT_NAMES`.  There
+        is no figure in velocity and none for an edge (the header says why).  A handle without the factor raises."""
+        return self._outlier_power(True, lamda, ncp, crit, strict)
+
+    def last_state_outlier_power_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_outlier_power_dyn_ms(self.h, byref(v)))
+        return v.value
+
     def reweight(self, alpha):
         """``vba_schur_reweight`` at the resident state (``include/vinsat_ba.h``): the reference's robust weights
         (``BA_filtering.py:21-25``) times the uploaded weights, written into the handle's weights on the device.  ``alpha`` in
@@ -484,6 +538,18 @@ def suspects(rel, crit, scaled=False):
     thr = float(crit) * (np.sqrt(rel["fit"]["s0sq"]) if scaled else 1.0)
     with np.errstate(invalid="ignore"):
         return np.nonzero(rel["wtest"] > thr)[0], np.nonzero(rel["lm_wtest"] > thr)[0]
+
+
+def scaled_power(power):
+    """The dict of :meth:`SchurBA.outlier_power` with ``mdb``, ``ext_pos``, ``ext_att``, ``ext_lm``, ``lm_mdb`` and ``lm_ext`` times
+    ``s0 = sqrt(fit["s0sq"])``, as ``ba.scaled_sigmas`` scales covariances: weights known up to their variance factor.  The
+    deletion figures come from the residuals and need no scale.  A copy; ``power`` is left as it is."""
+    s0 = float(np.sqrt(power["fit"]["s0sq"]))
+    out = dict(power)
+    for key in ("mdb", "ext_pos", "ext_att", "ext_lm", "lm_mdb", "lm_ext"):
+        out[key] = np.asarray(power[key]) * s0
+    out["s0"] = s0
+    return out
 
 
 def tile_bandwidth_of(structure, tile=64):
