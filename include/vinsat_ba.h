@@ -637,7 +637,9 @@ int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, flo
  * with the dynamics factor); 2: the 2 m keys |r| of the last vba_schur_reweight, sorted row order, row by row, u before v (VBA_ESTATE
  * if none since the upload).  On a handle with the dynamics factor (VBA_ESTATE without it) 3: the velocity step dv [n, 3] of the
  * last iterate; 4: the residuals r [n - 1, 6] and 5: the Jacobians D Phi [n - 1, 6, 6] of the edges at the state the last iterate
- * started from; 6: the edges' shares sigma_dyn |r|^2 [n - 1] of the cost there. */
+ * started from; 6: the edges' shares sigma_dyn |r|^2 [n - 1] of the cost there.  On a handle with the attitude factor (VBA_ESTATE
+ * without it), all at the state the last iterate started from, 7: the residuals a [n - 1, 3]; 8: the Jacobian pairs [n - 1, 2, 3, 3]
+ * (d a_i / d theta_i, then d a_i / d theta_{i+1}, row major); 9: the edges' shares sigma_att |a|^2 [n - 1] of the cost. */
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity);
 /* The orbit-dynamics factor with the velocities as unknowns, opt-in per handle, after vba_schur_upload.  time_idx [n]: the second
  * of every pose; every gap time_idx[i + 1] - time_idx[i] in 1 .. 64 (the domain of the sequential propagation; longer gaps stay
@@ -651,10 +653,30 @@ int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t cap
  * velocities, and the build time of vba_schur_last_ms includes the factor's kernels.  vba_schur_reweight, vba_schur_get_weights
  * and vba_schur_median work unchanged; vba_schur_covariance, vba_schur_reliability and vba_schur_snoop return VBA_ESTATE on such a
  * handle (their redundancy counts and gathers assume the 6 n system); vba_schur_covariance_dyn, vba_schur_reliability_dyn and
- * vba_schur_snoop_dyn are its queries.  A handle that never calls this behaves as before.
+ * vba_schur_snoop_dyn are its queries.  A handle that never calls this behaves as before.  (vba_schur_enable_attitude, below, adds
+ * a Gauss-Newton statement of the attitude term -- symmetric, so the Cholesky stands -- on a handle that has called this.)
  * Errors: VBA_EINVAL for n < 2, a gap outside 1 .. 64, a time_idx that does not increase, a sigma_dyn that is not positive and
  * finite; VBA_ESTATE before the upload or on a handle that has the factor already. */
 int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx /*[n]*/, double sigma_dyn);
+/* The Gauss-Newton attitude factor, opt-in per handle, after vba_schur_enable_dynamics.  cumrot [n][4]: the rotation accumulated over
+ * the gap after pose i (scalar last, as vba_host_gap_rotations gives it); row n - 1 is ignored.  Rows are used as given, not
+ * renormalised.  For every edge i -> i + 1, with (x) the Hamilton product:
+ *   [e, d] = conj(q_i (x) cumrot_i) (x) q_{i+1},   s = d >= 0 ? +1 : -1,   a_i = s e   (|a_i|^2 = 1 - d^2; d is the reference's d),
+ *   d a_i / d theta_{i+1} = 1/2 s (d I + [e]x),   d a_i / d theta_i = -1/2 s (L(conj cumrot_i) R(conj(q_i) (x) q_{i+1}))[0:3, 0:3]
+ * along the mode's retraction q <- normalise(q (x) qexp(dtheta)); weight sigma_att, Gauss-Newton: sigma_att J^T J into the attitude
+ * 3x3 blocks (rows and columns 6 i + 3 .. 6 i + 5) of the pose part, -sigma_att J^T a into the right-hand side; the cost gains
+ * sigma_att sum |a_i|^2.  These blocks are symmetric positive semidefinite (the Newton blocks of the fixed-landmark path are not),
+ * so the factorisation, the substitutions and the updates are unchanged.  The reference's term is sigma 100 (1 - |d|) =
+ * sigma 100 |a|^2 / (1 + |d|): sigma_att = sigma_dyn * 100 / 2 weights the attitude as the reference does near the solution.  With
+ * the factor the attitude of a pose without rows is held by its two edges and not by the damping alone.
+ * vba_schur_covariance_dyn includes the factor; vba_schur_reliability_dyn, vba_schur_snoop_dyn and vba_schur_outlier_power_dyn return
+ * VBA_ESTATE on such a handle (their redundancy counts and edge leverages do not know the 3 (n - 1) attitude equations);
+ * vba_schur_reweight, vba_schur_get_weights and vba_schur_median see rows only and work unchanged.  A handle that never calls this
+ * launches what it launched before and returns the same bits.
+ * Errors: VBA_EINVAL for a null pointer, a sigma_att that is not positive and finite, a cumrot row 0 .. n - 2 that is not finite or
+ * whose norm is further than 1e-6 from 1; VBA_ESTATE before the upload, on a handle without the dynamics factor, or on a handle that
+ * has the attitude factor already. */
+int vba_schur_enable_attitude(vba_schur_handle h, const double* cumrot /*[n][4]*/, double sigma_att);
 /* Covariances of the free-landmark system at the resident state: blocks of the inverse of H = [[B, E], [E^T, C]] as
  * vba_schur_iterate(h, lamda, ...) would build it there (lamda on every diagonal entry of B and C; lamda = 0, the usual
  * case, gives the undamped covariance -- the catalogue prior fixes the gauge).  With S = B - E C^-1 E^T and Y_k = E_k C_l^-1:
@@ -693,7 +715,7 @@ int vba_schur_last_covariance_ms(vba_schur_handle h, float* ms);
  * info, state_cov or edge_cov, lamda negative or NaN; VBA_ESTATE: before upload or before a state is set, or a handle without
  * the dynamics factor (vba_schur_covariance is the query of those; it, vba_schur_reliability and vba_schur_snoop keep refusing
  * a handle that has the factor).  The query changes nothing: it builds and factorises into scratch of its own, the residuals,
- * Jacobians and edge costs of its build included, so vba_schur_debug_fetch 3 .. 6 still report the last iterate; the following
+ * Jacobians and edge costs of its build included, so vba_schur_debug_fetch 3 .. 6 (and 7 .. 9 on a handle with the attitude factor, which the build includes) still report the last iterate; the following
  * iterates return the bits they would have returned without it.  Fixed order of operations: equal bits for equal problems.  Only
  * the tiles of S9^-1 that an output reads are formed; VBA_SCHUR_COV_FULL=1 in the environment at vba_schur_create forms all of
  * them by the kernel of vba_schur_covariance (comparison: the outputs have the same bits either way). */

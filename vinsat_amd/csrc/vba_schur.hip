@@ -28,6 +28,7 @@
 //   vba_schur_snoop.hip   vba_schur_snoop, vba_schur_snoop_dyn, vba_schur_rejected, vba_schur_snoop_restore and their passes
 //   vba_schur_robust.hip  vba_schur_reweight, vba_schur_get_weights, vba_schur_median and their passes
 //   vba_schur_dyn.hip     vba_schur_enable_dynamics and the kernels of the factor
+//   vba_schur_att.hip     vba_schur_enable_attitude and the kernels of the Gauss-Newton attitude factor (bodies: vba_schur_att_math.h)
 //
 // Kernels (all reductions in a fixed order -- no float atomics):
 //   k_lm_blocks     thread per landmark: C_l, w_l over its rows, C_l^-1, then E_k and Y_k = E_k C_l^-1 per row
@@ -65,6 +66,8 @@
 // Robust re-weighting (vba_schur_reweight, vba_schur_median: the passes of vba_schur_robust.hip)
 // Orbit-dynamics factor with velocity unknowns (vba_schur_enable_dynamics: the kernels of vba_schur_dyn.hip; the reduced system
 // becomes [6 n pose | 3 n velocity] unknowns, the build and factor kernels fill and factorise it unchanged)
+// Gauss-Newton attitude factor on such a handle (vba_schur_enable_attitude: the kernels of vba_schur_att.hip behind those of the orbit
+// factor, in the build and in the cost; symmetric positive semidefinite blocks on the attitude unknowns, the same Cholesky)
 #include "vba_schur_context.h"
 
 namespace {
@@ -208,15 +211,19 @@ void schur_scratch_release(SchurScratch& Z) {
 static int schur_cost(vba_schur_handle h, const double* states, const double* X, double* cost) {
     SchurView V = h->V;
     SchurDyn& D = h->dyn;
+    SchurAtt& T = h->att;
     hipLaunchKernelGGL(k_cost, dim3(V.npart), dim3(256), 0, h->stream, V, states, X);
     if (D.enabled) schur_dyn_cost_launch(schur_dyn_view(h, V), states, h->stream);
+    if (T.enabled) schur_att_cost_launch(schur_att_view(h, V), states, h->stream);
     SCHK(hipGetLastError());
     SCHK(hipMemcpyAsync(h->h_part.data(), V.part, (size_t)V.npart * 8, hipMemcpyDeviceToHost, h->stream));
     if (D.enabled) SCHK(hipMemcpyAsync(D.h_part.data(), D.part, (size_t)D.npart * 8, hipMemcpyDeviceToHost, h->stream));
+    if (T.enabled) SCHK(hipMemcpyAsync(T.h_part.data(), T.part, (size_t)T.npart * 8, hipMemcpyDeviceToHost, h->stream));
     SCHK(hipStreamSynchronize(h->stream));
     double s = 0.0;
     for (int b = 0; b < V.npart; ++b) s += h->h_part[b];      // fixed order
     if (D.enabled) for (int b = 0; b < D.npart; ++b) s += D.h_part[b];     // ... the dynamics partials after the rows' and the prior's
+    if (T.enabled) for (int b = 0; b < T.npart; ++b) s += T.h_part[b];     // ... and the attitude partials after those
     *cost = s;
     return VBA_OK;
 }
@@ -224,12 +231,13 @@ static int schur_cost(vba_schur_handle h, const double* states, const double* X,
 // Build the reduced camera system of the view's state and damping and factorise it, on stream s (the bulk of a panel's trailing
 // update beside it on h->aux): S, g, Cinv, wl, E, Y, invL and *d_info are the view's and the caller's, so vba_schur_iterate runs it
 // on the handle's arrays and vba_schur_covariance on scratch of its own.  ev_built (if given) is recorded between the two parts;
-// dyn (if given) stands for the handle's dynamics arrays in the build.
-int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn) {
+// dyn and att (if given) stand for the handle's dynamics and attitude arrays in the build.
+int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn,
+                       const SchurAttView* att) {
     SCHK(hipMemsetAsync(V.S, 0, (size_t)V.Npad * V.Npad * 8, s));
     SCHK(hipMemsetAsync(V.g, 0, (size_t)V.Npad * 8, s));
     SCHK(hipMemsetAsync(d_info, 0, 4, s));
-    schur_build_launch(h, V, s, dyn);
+    schur_build_launch(h, V, s, dyn, att);
     if (ev_built) SCHK(hipEventRecord(ev_built, s));
     return schur_factor_launch(h, V, s, d_info);
 }
@@ -303,6 +311,7 @@ int vba_schur_destroy(vba_schur_handle h) {
     if (h->ev_bulk) hipEventDestroy(h->ev_bulk);
     for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
     if (h->dyn.arena) hipFree(h->dyn.arena);
+    if (h->att.arena) hipFree(h->att.arena);
     for (SchurScratch* z : {&h->robust.sc, &h->snoop.sc, &h->pow.sc, &h->rel.sc, &h->q.sc}) schur_scratch_release(*z);
     if (h->arena) hipFree(h->arena);
     delete h;
@@ -434,7 +443,8 @@ int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, flo
 // what: 0 = step of the last iteration [6 n + 3 L] (dc then dl), 1 = lower triangle of the Cholesky factor as a dense
 // [N][N] row-major matrix (upper part zero; N = 6 n, or 9 n with the dynamics factor), 2 = the 2 m keys |r| of the last
 // re-weighting; with the dynamics factor 3 = dv [n][3] of the last iteration, 4 = r [n - 1][6], 5 = D Phi [n - 1][6][6] and
-// 6 = sigma_dyn |r_e|^2 [n - 1] of its build
+// 6 = sigma_dyn |r_e|^2 [n - 1] of its build; with the attitude factor 7 = a [n - 1][3], 8 = the Jacobian pairs [n - 1][2][3][3] and
+// 9 = sigma_att |a_e|^2 [n - 1] of its build
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity) {
     if (!h || !out) return sfail(VBA_EINVAL, "null argument");
     SCHK(hipSetDevice(h->device));
@@ -455,6 +465,16 @@ int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t cap
         const int64_t count[4] = {3 * n, 6 * (n - 1), 36 * (n - 1), n - 1};
         if (capacity < count[what - 3]) return sfail(VBA_EINVAL, "buffer too small");
         SCHK(hipMemcpy(out, src[what - 3], (size_t)count[what - 3] * 8, hipMemcpyDeviceToHost));
+        return VBA_OK;
+    }
+    if (what >= 7 && what <= 9) {
+        const SchurAtt& T = h->att;
+        if (!T.enabled) return sfail(VBA_ESTATE, "the attitude factor is not enabled on this handle");
+        const int64_t ne = (int64_t)V.n - 1;
+        const double* src[3] = {T.a, T.J, T.ecost};
+        const int64_t count[3] = {3 * ne, 18 * ne, ne};
+        if (capacity < count[what - 7]) return sfail(VBA_EINVAL, "buffer too small");
+        SCHK(hipMemcpy(out, src[what - 7], (size_t)count[what - 7] * 8, hipMemcpyDeviceToHost));
         return VBA_OK;
     }
     if (what == 1) {

@@ -139,7 +139,7 @@ __global__ void k_pad_identity(SchurView V) {
 
 }  // namespace
 
-void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn) {
+void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn, const SchurAttView* att) {
     hipLaunchKernelGGL(k_lm_blocks, dim3((V.L + 255) / 256), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pose_blocks, dim3((V.n + 15) / 16), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pair_blocks, dim3(V.nblk), dim3(64), 0, s, V);
@@ -147,6 +147,11 @@ void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, c
         const SchurDynView W = dyn ? *dyn : schur_dyn_view(h, V);
         schur_dyn_edges_launch(W, V.states, s);
         schur_dyn_scatter_launch(W, s);
+        if (h->att.enabled) {   // the attitude blocks behind them: symmetric positive semidefinite, on the attitude unknowns alone
+            const SchurAttView T = att ? *att : schur_att_view(h, V);
+            schur_att_edges_launch(T, V.states, s);
+            schur_att_scatter_launch(T, s);
+        }
     }
     if (V.Npad > V.N) hipLaunchKernelGGL(k_pad_identity, dim3((V.Npad - V.N + 63) / 64), dim3(64), 0, s, V);
 }

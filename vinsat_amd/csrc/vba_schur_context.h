@@ -221,6 +221,22 @@ struct SchurDyn {
     std::vector<double> h_part;
 };
 
+// State of vba_schur_enable_attitude: the gap rotations, the factor of the last build and the partials of its cost, and (q_*) the
+// arrays vba_schur_covariance_dyn builds into, so that a, J, ecost stay those of the last iterate.  One allocation.
+struct SchurAtt {
+    char* arena = nullptr;
+    bool enabled = false;
+    double sigma = 0.0;
+    double *cumrot = nullptr, *a = nullptr, *J = nullptr, *ecost = nullptr, *part = nullptr;
+    double *q_a = nullptr, *q_J = nullptr, *q_ecost = nullptr, *q_part = nullptr;
+    int npart = 0;
+    std::vector<double> h_part;
+};
+
+// why vba_schur_reliability_dyn, vba_schur_snoop_dyn and vba_schur_outlier_power_dyn refuse a handle with the attitude factor
+constexpr char kAttRefusal[] = " is not available on a handle with the attitude factor: its redundancy counts and edge leverages do not "
+                               "know the 3 (n - 1) attitude equations";
+
 // why the three queries refuse a handle with the dynamics factor (vba_schur_covariance_dyn is the covariance query of such a handle)
 constexpr char kDynRefusal[] = " is not available on a handle with the dynamics factor: its redundancy counts and gathers assume the "
                                "6 n reduced system of the reprojection rows";
@@ -250,14 +266,16 @@ struct vba_schur_context {
     SchurSnoop snoop;           // vba_schur_snoop's state (nothing until the first snoop)
     SchurRobust robust;         // vba_schur_reweight's state (nothing until the first re-weighting)
     SchurDyn dyn;               // vba_schur_enable_dynamics' state (nothing on a handle without the dynamics factor)
+    SchurAtt att;               // vba_schur_enable_attitude's state (nothing on a handle without the attitude factor)
     int bw = 1 << 30;           // tile bandwidth of the reduced system (max |I - J| over its non-zero tiles), from the block list
 };
 
 // ---- vba_schur_build.hip
 // S, g, Cinv, wl, E, Y of the view's state and damping on stream s (S and g zeroed by the caller): the reprojection blocks, the
-// dynamics blocks on a handle with the factor, the identity of the padding rows.  dyn (if given) replaces the handle's own dynamics
-// arrays: the covariance query of such a handle builds r, A, ecost in its scratch and leaves the handle's as the last iterate wrote them
-void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn = nullptr);
+// dynamics blocks on a handle with the factor (the attitude blocks behind them on a handle with that factor too), the identity of the
+// padding rows.  dyn (if given) replaces the handle's own dynamics arrays: the covariance query of such a handle builds r, A, ecost in
+// its scratch and leaves the handle's as the last iterate wrote them; att (if given) does the same for the attitude arrays
+void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn = nullptr, const SchurAttView* att = nullptr);
 
 // ---- vba_schur_factor.hip
 // S = Lg Lg^T in place and the inverse diagonal factors, on stream s (the bulk of a panel's trailing update beside it on h->aux);
@@ -265,7 +283,8 @@ void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, c
 int schur_factor_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info);
 
 // ---- vba_schur.hip
-int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn = nullptr);
+int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn = nullptr,
+                       const SchurAttView* att = nullptr);
 
 // ---- vba_schur_cov.hip
 int schur_query_alloc(vba_schur_handle h);
@@ -286,4 +305,8 @@ void schur_pow_rows_launch(vba_schur_handle h, const SchurView& V, double ncp);
 // ---- vba_schur_dyn.hip
 // the dynamics arrays of a handle with the factor enabled, at the damping of the view
 SchurDynView schur_dyn_view(vba_schur_handle h, const SchurView& V);
+
+// ---- vba_schur_att.hip
+// the attitude arrays of a handle with that factor enabled; query: the arrays of vba_schur_covariance_dyn's build in their place
+SchurAttView schur_att_view(vba_schur_handle h, const SchurView& V, bool query = false);
 #pragma GCC visibility pop

@@ -328,8 +328,10 @@ int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEv
     V = query_view(h, lamda);
     SchurDynView DW = schur_dyn_view(h, V);
     DW.r = Q.dyn_r; DW.A = Q.dyn_A; DW.ecost = Q.dyn_ecost; DW.part = Q.dyn_part;
+    // (a handle with the attitude factor: the arrays that factor keeps for this build, so debug_fetch 7 .. 9 stay the last iterate's)
+    const SchurAttView TW = h->att.enabled ? schur_att_view(h, V, true) : SchurAttView{};
     SCHK(hipEventRecord(ev_begin, s));
-    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr, &DW)) return rc;
+    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr, &DW, h->att.enabled ? &TW : nullptr)) return rc;
     SCHK(hipGetLastError());
     *bad = 0;
     SCHK(hipMemcpyAsync(bad, Q.info, 4, hipMemcpyDeviceToHost, s));

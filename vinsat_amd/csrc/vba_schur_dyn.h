@@ -32,4 +32,25 @@ void schur_dyn_update_launch(const SchurDynView& W, const double* states, double
 // part[b] = sum over the edges of block b of sigma |r_e|^2 at `states` (residual-only propagation), fixed order
 void schur_dyn_cost_launch(const SchurDynView& W, const double* states, hipStream_t s);
 
+// The Gauss-Newton attitude factor on top of it (vba_schur_enable_attitude; kernels: vba_schur_att.hip, bodies: vba_schur_att_math.h)
+struct SchurAttView {
+    int n, Npad;
+    double sigma;                   // sigma_att
+    const double* cumrot;           // [n][4] rotation accumulated over the gap after pose i (row n - 1 unused), checked on the host
+    double* a;                      // [n - 1][3] residual of the last build
+    double* J;                      // [n - 1][2][3][3] d a / d theta_i, then d a / d theta_{i+1}, of the last build
+    double* ecost;                  // [n - 1] sigma |a_e|^2 of the last build
+    double* part;                   // [npart] block partials of the attitude cost, one per 256 edges (schur_dyn_partials)
+    int npart;
+    double* S;                      // the reduced system and its right-hand side, as in SchurDynView
+    double* g;
+};
+
+// a, J, ecost at `states` [n][10]: thread per edge
+void schur_att_edges_launch(const SchurAttView& W, const double* states, hipStream_t s);
+// the factor's blocks into S and g, after schur_dyn_scatter_launch on the same stream; no atomics, fixed order
+void schur_att_scatter_launch(const SchurAttView& W, hipStream_t s);
+// part[b] = sum over the edges of block b of sigma |a_e|^2 at `states`, fixed order
+void schur_att_cost_launch(const SchurAttView& W, const double* states, hipStream_t s);
+
 }  // namespace vba

@@ -1,6 +1,7 @@
 // vba_schur_dyn.hip -- the orbit-dynamics factor of the free-landmark mode (vba_schur_enable_dynamics; ADD-ON, PARITY UNPINNED as
-// the rest of the mode: vba_schur.hip carries the map of the units): its kernels, then the entry point.  Model, unknown order and the scatter's work items: vba_schur_dyn_math.h.  The attitude factor stays
-// out (its Newton blocks are not symmetric; this mode's solver is a Cholesky).
+// the rest of the mode: vba_schur.hip carries the map of the units): its kernels, then the entry point.  Model, unknown order and the scatter's work items: vba_schur_dyn_math.h.  The attitude factor of the
+// fixed-landmark path stays out (its Newton blocks are not symmetric; this mode's solver is a Cholesky); vba_schur_att.hip adds a
+// Gauss-Newton statement of it, opt-in, on a handle that has this factor.
 //
 // Kernels (no float atomics; every sum in a fixed order, so two runs and two handles leave the same bits):
 //   k_sdyn_edges    eight lanes per edge, six of them at work: lane c propagates the edge's start state with the tangent e_c

@@ -8,7 +8,7 @@
 //     J_e = [A_e at pose i | -D at pose i + 1],   A_e = D Phi_e
 // Gauss-Newton with weight sigma:  H += sigma J^T J,  g -= sigma J^T r,  cost += sigma |r|^2.
 // The ATTITUDE factor of the fixed-landmark path is NOT part of this mode: its Newton blocks (Hd, Hu, Hl) are not symmetric and the
-// reduced system of this mode is factorised by a Cholesky.
+// reduced system of this mode is factorised by a Cholesky.  (vba_schur_att_math.h: the Gauss-Newton statement that is.)
 //
 // Unknowns of the reduced system: [6 n pose unknowns (dp, dtheta per pose) | 3 n velocity unknowns]; component c of the dynamics
 // state x_i = (p_i, v_i) is unknown 6 i + c for c < 3 and 6 n + 3 i + (c - 3) for c >= 3.  Only the lower triangle is stored: an

@@ -181,6 +181,7 @@ int schur_power_call(vba_schur_handle h, bool dyn, double lamda, double ncp, dou
     if (!(crit > 0.0)) return sfail(VBA_EINVAL, "crit must be > 0 (+inf counts nothing)");
     if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
     if (dyn && !h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
+    if (h->att.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_outlier_power_dyn") + kAttRefusal);
     SCHK(hipSetDevice(h->device));
     if (int rc = schur_query_alloc(h)) return rc;
     if (int rc = schur_query_index(h)) return rc;

@@ -232,6 +232,7 @@ int vba_schur_reliability_dyn(vba_schur_handle h, double lamda, double* leverage
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
     if (!h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
+    if (h->att.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_reliability_dyn") + kAttRefusal);
     SCHK(hipSetDevice(h->device));
     if (int rc = schur_query_alloc(h)) return rc;
     if (int rc = schur_query_index(h)) return rc;

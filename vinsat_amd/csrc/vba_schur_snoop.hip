@@ -170,6 +170,7 @@ static int schur_snoop_call(vba_schur_handle h, bool dyn, double lamda, double c
     if (min_rows < 0 || min_track < 0) return sfail(VBA_EINVAL, "min_rows and min_track must be >= 0");
     if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
     if (dyn && !h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
+    if (h->att.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_snoop_dyn") + kAttRefusal);
     SCHK(hipSetDevice(h->device));
     if (int rc = schur_query_alloc(h)) return rc;
     if (int rc = schur_query_index(h)) return rc;

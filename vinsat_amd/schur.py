@@ -7,7 +7,8 @@ landmark blocks are eliminated (3x3 inversions), and the dense reduced camera sy
 (``vinsat_amd/csrc/vba_schur*.hip``, one unit per stage; ``vba_schur.hip`` heads them with the map).  It is validated against ``oracle/schur_oracle.py`` -- this repository's own CPU
 restatement -- only, and it never runs inside :func:`vinsat_amd.ba.BA`.  Opt-in per handle (``time_idx=``, ``sigma_dyn=``) the
 reference's J2 orbit factor ties consecutive poses and the velocities become unknowns (``vinsat_amd/csrc/vba_schur_dyn.hip``,
-DESIGN 9.5); the attitude factor is not part of it.
+DESIGN 9.5).  On top of that, opt-in too (``cumrot=``, ``sigma_att=``), a Gauss-Newton statement of the reference's attitude term
+ties consecutive attitudes through the gyro's gap rotations (``vinsat_amd/csrc/vba_schur_att.hip``).
 
 Host side (this file): the static structure of a window -- rows sorted by landmark, the rows of each pose, and for every
 6x6 block of the reduced system the list of row pairs that share a landmark -- is built once with NumPy and uploaded.
@@ -107,12 +108,19 @@ class SchurBA:
     """Device-resident free-landmark BA problem: ``n`` poses, ``L`` landmarks, ``m`` observation rows."""
 
     def __init__(self, states, landmarks0, uv, weights, pose_of_row, landmark_of_row, intrinsics, sigma_prior=0.05, device=0,
-                 time_idx=None, sigma_dyn=None):
+                 time_idx=None, sigma_dyn=None, cumrot=None, sigma_att=None):
         """``time_idx [n]`` (the second of every pose) and ``sigma_dyn`` together switch on the orbit-dynamics factor with the
-        velocities as unknowns (``vba_schur_enable_dynamics`` in ``include/vinsat_ba.h``: gaps of 1 .. 64 s, no attitude
-        factor); with neither the handle is the purely visual bundle adjustment."""
+        velocities as unknowns (``vba_schur_enable_dynamics`` in ``include/vinsat_ba.h``: gaps of 1 .. 64 s); with neither the
+        handle is the purely visual bundle adjustment.  ``cumrot [n,4]`` (the rotation accumulated over the gap after every pose,
+        scalar last, as ``od_pipe.gap_rotations`` gives it; the last row is ignored) and ``sigma_att`` together add the
+        Gauss-Newton attitude factor on such a handle (``vba_schur_enable_attitude``); ``sigma_att = sigma_dyn * QUAT_COEFF / 2``
+        weights the attitude as the reference does near the solution."""
         if (time_idx is None) != (sigma_dyn is None):
             raise ValueError("time_idx and sigma_dyn switch on the dynamics factor together: give both or neither")
+        if (cumrot is None) != (sigma_att is None):
+            raise ValueError("cumrot and sigma_att switch on the attitude factor together: give both or neither")
+        if cumrot is not None and time_idx is None:
+            raise ValueError("the attitude factor (cumrot, sigma_att) is only valid together with time_idx and sigma_dyn")
         self.lib = _lib.load()
         states = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10)
         X0 = np.ascontiguousarray(landmarks0, dtype=np.float64).reshape(-1, 3)
@@ -139,6 +147,16 @@ class SchurBA:
                 if t.size != self.n:
                     raise ValueError("time_idx needs one entry per pose")
                 self._check(self.lib.vba_schur_enable_dynamics(self.h, t.ctypes.data_as(ctypes.POINTER(c_int)), float(sigma_dyn)))
+            except Exception:
+                self.close()
+                raise
+        self.attitude = cumrot is not None
+        if self.attitude:
+            try:
+                c = np.ascontiguousarray(cumrot, dtype=np.float64)
+                if c.shape != (self.n, 4):
+                    raise ValueError("cumrot needs one quaternion per pose")
+                self._check(self.lib.vba_schur_enable_attitude(self.h, c.ctypes.data_as(PD), float(sigma_att)))
             except Exception:
                 self.close()
                 raise
@@ -214,6 +232,19 @@ class SchurBA:
         """``sigma_dyn |r|^2 [n-1]``: the edges' shares of the cost at the state the last iterate started from."""
         return self._dynamics_fetch(6, (self.n - 1,))
 
+    def attitude_residual(self):
+        """``a [n-1,3]`` of the edges at the state the last iterate started from (a handle with the attitude factor)."""
+        return self._dynamics_fetch(7, (self.n - 1, 3))
+
+    def attitude_jacobian(self):
+        """``[n-1,2,3,3]``: ``d a_i / d theta_i``, then ``d a_i / d theta_{i+1}``, of the edges at the state the last iterate
+        started from (a handle with the attitude factor)."""
+        return self._dynamics_fetch(8, (self.n - 1, 2, 3, 3))
+
+    def attitude_edge_cost(self):
+        """``sigma_att |a|^2 [n-1]``: the edges' shares of the cost at the state the last iterate started from."""
+        return self._dynamics_fetch(9, (self.n - 1,))
+
     def cholesky_factor(self):
         """The factor of the last iterate, dense lower triangular: ``[6n, 6n]``, or ``[9n, 9n]`` over ``[pose | velocity]``
         unknowns on a handle with the dynamics factor."""
@@ -257,7 +288,8 @@ class SchurBA:
         ``Sigma(x_i, x_{i+1})`` (rows of pose ``i``, columns of pose ``i + 1``), ``landmark [L,3,3]`` in the caller's landmark
         order, ``info``, and with ``pairs`` also ``pairs = (blk_i, blk_j, [nblk,6,6])`` as :meth:`covariance` returns them.  Up to
         the variance factor of the weights.  Nothing on the handle changes: state, step, factor, the dynamics arrays of the last
-        iterate and the bits of the following iterates.
+        iterate and the bits of the following iterates.  On a handle with the attitude factor the system includes it (and a window
+        with a pose without rows is positive definite at ``lamda = 0``).
 
         ``strict`` as in :meth:`covariance`: a system that is not positive definite raises ``VbaError`` naming the row
         (``info - 1``), or gives NaN everywhere.  A handle without the dynamics factor raises: :meth:`covariance` is its query."""
@@ -353,7 +385,9 @@ class SchurBA:
         edges.  There is no w-test of an edge (the header says why).  :func:`suspects` reads the dict unchanged.  Nothing on the
         handle changes.
 
-        ``strict`` as in :meth:`state_covariance`.  A handle without the dynamics factor raises: :meth:`reliability` is its query."""
+        ``strict`` as in :meth:`state_covariance`.  A handle without the dynamics factor raises: :meth:`reliability` is its query.
+        A handle with the attitude factor raises too, as do :meth:`state_snoop` and :meth:`state_outlier_power`: their redundancy
+        counts and edge leverages do not know the attitude equations."""
         ne = max(self.n - 1, 0)
         out = dict(leverage=np.empty(self.m), wtest=np.empty(self.m), lm_leverage=np.empty(self.L), lm_wtest=np.empty(self.L),
                    lm_stats=np.empty((self.L, 3)), pose_stats=np.empty((self.n, 3)), edge_leverage=np.empty(ne), edge_omega=np.empty(ne))
