@@ -670,7 +670,8 @@ int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx /*[n]*/, d
  * sigma 100 |a|^2 / (1 + |d|): sigma_att = sigma_dyn * 100 / 2 weights the attitude as the reference does near the solution.  With
  * the factor the attitude of a pose without rows is held by its two edges and not by the damping alone.
  * vba_schur_covariance_dyn includes the factor; vba_schur_reliability_dyn, vba_schur_snoop_dyn and vba_schur_outlier_power_dyn return
- * VBA_ESTATE on such a handle (their redundancy counts and edge leverages do not know the 3 (n - 1) attitude equations);
+ * VBA_ESTATE on such a handle (their redundancy counts and edge leverages do not know the 3 (n - 1) attitude equations):
+ * vba_schur_reliability_att, vba_schur_snoop_att and vba_schur_outlier_power_att are its queries, and count them;
  * vba_schur_reweight, vba_schur_get_weights and vba_schur_median see rows only and work unchanged.  A handle that never calls this
  * launches what it launched before and returns the same bits.
  * Errors: VBA_EINVAL for a null pointer, a sigma_att that is not positive and finite, a cumrot row 0 .. n - 2 that is not finite or
@@ -893,6 +894,71 @@ int vba_schur_outlier_power_dyn(vba_schur_handle h, double lamda, double ncp, do
                                 double* fit /*[14] or NULL*/, int* info);
 /* HIP-event time of the last vba_schur_outlier_power_dyn on this handle */
 int vba_schur_last_outlier_power_dyn_ms(vba_schur_handle h, float* ms);
+/* Reliability on a handle with the dynamics factor AND the attitude factor (vba_schur_enable_attitude), at the resident state: the
+ * query of vba_schur_reliability_dyn with the 3 (n - 1) attitude equations counted, and a test of every attitude edge -- which gyro
+ * gap rotation the window contradicts.  H = [[B9, E9], [E9^T, C]] is as vba_schur_covariance_dyn(h, lamda, ...) builds it on this
+ * handle, both factors included, Sigma = H^-1.
+ *   leverage, wtest, lm_leverage, lm_wtest, lm_stats, pose_stats: word for word as vba_schur_reliability defines them (the NaN
+ *   rules, the w == 0 rule and the closed form of a landmark without rows included), with the Sigma_ii, Sigma_il and Sigma_ll blocks
+ *   of THIS Sigma, as vba_schur_reliability_dyn takes them from its own.
+ *   edge_leverage, edge_omega: the orbit edges, as vba_schur_reliability_dyn defines them, from the state_cov / edge_cov of THIS
+ *   Sigma.  Still no w-test of an orbit edge, for the reason given there.
+ *   Attitude edge i (pose i -> pose i + 1) is a 3-row observation of weight sigma_att with J_i = [J_own | J_next] (3x6) over
+ *   x = [dtheta_i, dtheta_{i+1}] and the residual a_i (vba_schur_enable_attitude), both of the query's own build at the resident
+ *   state; Sigma6 = the components {3, 4, 5} of state_cov[i], edge_cov[i] (rows of pose i, columns of pose i + 1; the lower left of
+ *   Sigma6 is the transpose of the same stored block) and state_cov[i + 1] of vba_schur_covariance_dyn; P_a = sigma_att J_i Sigma6 J_i^T:
+ *     att_leverage[i] = tr P_a in (0, 3]  (each diagonal entry on its own, summed in index order),
+ *     att_omega[i]    = sigma_att |a_i|^2,
+ *     att_wtest[i]    = sqrt(sigma_att a_i^T (I - P_a)^-1 a_i)  with the symmetric part of I - P_a, by cofactors over the determinant
+ *                       as lm_wtest; NaN where the determinant is not positive or the quadratic form is negative or not finite.
+ *   This test exists where the orbit edge's does not: an attitude edge keeps nearly all of its three units of redundancy (leverage
+ *   4e-4 .. 9e-3 of 3 at sigma_att = 5e5 on windows whose poses all have rows; 1.5 on each of the two edges around a pose without
+ *   rows, which alone determine that pose's attitude), the smallest eigenvalue of I - P_a is at least 0.49, and two NumPy routes
+ *   to the test agree to 3e-14.  An edge next to a bad gap rotation absorbs part of it: the bad gap ranks first, its neighbours
+ *   follow.  Edges of either kind are never rejected.
+ *   fit[13] = {Omega = rows, priors, orbit edges and attitude edges: the cost of vba_schur_iterate on this handle, in a summation
+ *              order of its own; m_eff; t_rows; t_prior;
+ *              rho = 2 m_eff + 3 L + 6 (n - 1) + 3 (n - 1) - t_rows - t_prior - t_edges - t_att; s0sq = Omega / rho (NaN if rho <= 0);
+ *              largest finite row wtest; largest finite landmark wtest; t_edges; Omega_edges; t_att = sum att_leverage;
+ *              Omega_att = sum att_omega; largest finite att_wtest}: slots 0 .. 9 are those of vba_schur_reliability_dyn.  The traces
+ *              obey t_rows + t_prior + t_edges + t_att + lamda tr(H^-1) = 9 n + 3 L; at lamda = 0 with every weight positive
+ *              rho = 2 m - 9.
+ * Any output may be NULL, in any combination; what is asked for decides the copies only.  *info, the NaN-everywhere rule and the
+ * error codes are those of vba_schur_reliability_dyn; a handle without the attitude factor gets VBA_ESTATE (vba_schur_reliability_dyn
+ * or vba_schur_reliability is its query; both keep refusing a handle that has the factor).  The query changes nothing: state,
+ * last_info, last_ms, debug_fetch 3 .. 9 and last_covariance_dyn_ms read as before, and the following iterates and
+ * vba_schur_covariance_dyn queries return the bits they would have returned without it.  No float atomics, every sum has one order:
+ * equal problems give equal bits. */
+int vba_schur_reliability_att(vba_schur_handle h, double lamda, double* leverage /*[m] or NULL*/, double* wtest /*[m] or NULL*/,
+                              double* lm_leverage /*[L] or NULL*/, double* lm_wtest /*[L] or NULL*/, double* lm_stats /*[L][3] or NULL*/,
+                              double* pose_stats /*[n][3] or NULL*/, double* edge_leverage /*[n-1] or NULL*/,
+                              double* edge_omega /*[n-1] or NULL*/, double* att_leverage /*[n-1] or NULL*/, double* att_wtest /*[n-1] or NULL*/,
+                              double* att_omega /*[n-1] or NULL*/, double* fit /*[13] or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_reliability_att on this handle (the device part of vba_schur_covariance_dyn and the passes) */
+int vba_schur_last_reliability_att_ms(vba_schur_handle h, float* ms);
+/* Data snooping on a handle with both factors: the rule of vba_schur_snoop, steps 1 to 3 as they stand, with the same counts,
+ * crit_used, min_rows and min_track, fed by the device part of vba_schur_reliability_att(h, lamda, ...); with scaled it uses that
+ * query's fit[5], which counts the attitude equations.  Edges of either kind are never rejected: a gyro suspect (att_wtest) is
+ * reported by the reliability query, not acted on.  vba_schur_rejected and vba_schur_snoop_restore serve this snoop too.  From the
+ * call's return the handle gives, bit for bit, what a fresh handle gives that has the same structure, the same factors, those rows'
+ * weights zeroed and the same state (vba_schur_iterate, vba_schur_covariance_dyn, vba_schur_reliability_att).  A call that rejects
+ * nothing changes nothing.  Errors: as vba_schur_snoop_dyn, and VBA_ESTATE on a handle without the attitude factor. */
+int vba_schur_snoop_att(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts /*[3] or NULL*/,
+                        double* crit_used /*or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_snoop_att on this handle */
+int vba_schur_last_snoop_att_ms(vba_schur_handle h, float* ms);
+/* vba_schur_outlier_power on a handle with both factors: every quantity of vba_schur_outlier_power with the blocks of the Sigma of
+ * vba_schur_reliability_att(h, lamda, ...) -- the same row and prior formulas, the same degenerate rules and promises.  fit[17] =
+ * the fit[13] of vba_schur_reliability_att with its bits, edges of both kinds included, then the four slots of
+ * vba_schur_outlier_power; pose_fit[i][1] has the bits of that query's pose_stats[i][0].  There is no power figure for an edge of
+ * either kind: the detectable bias of a gap rotation is not provided.  VBA_ESTATE on a handle without the attitude factor. */
+int vba_schur_outlier_power_att(vba_schur_handle h, double lamda, double ncp, double crit, double* mdb /*[m] or NULL*/,
+                                double* ext_pos /*[m] or NULL*/, double* ext_att /*[m] or NULL*/, double* ext_lm /*[m] or NULL*/,
+                                double* del_pos /*[m] or NULL*/, double* del_lm /*[m] or NULL*/, double* lm_mdb /*[L] or NULL*/,
+                                double* lm_ext /*[L] or NULL*/, double* lm_del_pos /*[L] or NULL*/, double* pose_fit /*[n][4] or NULL*/,
+                                double* fit /*[17] or NULL*/, int* info);
+/* HIP-event time of the last vba_schur_outlier_power_att on this handle */
+int vba_schur_last_outlier_power_att_ms(vba_schur_handle h, float* ms);
 /* Robust re-weighting of the free-landmark fit: the reference's weights (BA_filtering.py:21-25) at the resident state, written
  * into the handle's weight array in place, on the device.  The reference computes them once per BA() call and holds them through
  * its LM trials; here the caller decides when (vinsat_amd/schur.py: solve(robust=...)).

@@ -113,6 +113,12 @@ SIGNATURES = {
     "vba_schur_last_outlier_power_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_outlier_power_dyn": (c_int, [c_void_p, c_double, c_double, c_double] + [PD] * 11 + [POINTER(c_int)]),
     "vba_schur_last_outlier_power_dyn_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_reliability_att": (c_int, [c_void_p, c_double] + [PD] * 12 + [POINTER(c_int)]),
+    "vba_schur_last_reliability_att_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_snoop_att": (c_int, [c_void_p, c_double, c_double, c_int, c_int, c_int, POINTER(c_int), PD, POINTER(c_int)]),
+    "vba_schur_last_snoop_att_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "vba_schur_outlier_power_att": (c_int, [c_void_p, c_double, c_double, c_double] + [PD] * 11 + [POINTER(c_int)]),
+    "vba_schur_last_outlier_power_att_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_reweight": (c_int, [c_void_p, c_double, PD, PD, POINTER(c_int)]),
     "vba_schur_get_weights": (c_int, [c_void_p, PD, PD]),
     "vba_schur_last_reweight_ms": (c_int, [c_void_p, POINTER(c_float)]),

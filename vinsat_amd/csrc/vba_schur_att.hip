@@ -108,6 +108,10 @@ extern "C" int vba_schur_enable_attitude(vba_schur_handle h, const double* cumro
         hipFree(A);
         return sfail(VBA_EHIP, "attitude factor: hipMemset / upload failed");
     }
+    // the reliability scratch of a query before this call has no room for the attitude edges, so it goes: vba_schur_reliability_dyn
+    // refuses this handle from now on, and vba_schur_reliability_att allocates it anew
+    schur_scratch_release(h->rel.sc);
+    h->rel = SchurRel{};
     T.arena = A; T.sigma = sigma_att; T.npart = npart;
     T.cumrot = (double*)(A + o_c);
     T.a = (double*)(A + o_a); T.J = (double*)(A + o_J); T.ecost = (double*)(A + o_ec); T.part = (double*)(A + o_part);

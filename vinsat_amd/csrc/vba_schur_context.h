@@ -170,17 +170,18 @@ struct SchurQuery {
 };
 
 // What vba_schur_reliability needs beyond that, allocated by the first reliability query of a handle: its outputs on the device,
-// the per-row and per-landmark cost terms of the totals, and two timing events of its own.  fit has the ten slots of
-// vba_schur_reliability_dyn (the plain query fills and copies eight); elev [n - 1], the edge leverages, exists on a handle with the
-// dynamics factor only.
+// the per-row and per-landmark cost terms of the totals, and two timing events of its own.  fit has the thirteen slots of
+// vba_schur_reliability_att (the plain query fills and copies eight, vba_schur_reliability_dyn ten); elev [n - 1], the edge
+// leverages, exists on a handle with the dynamics factor only; alev, awt [n - 1], leverage and w-test of the attitude edges, on a
+// handle with the attitude factor only.
 struct SchurRel {
     SchurScratch sc;
     double *lev = nullptr, *wt = nullptr, *om = nullptr, *lmlev = nullptr, *lmwt = nullptr, *lmom = nullptr, *lm_stats = nullptr,
-           *pose_stats = nullptr, *fit = nullptr, *elev = nullptr;
+           *pose_stats = nullptr, *fit = nullptr, *elev = nullptr, *alev = nullptr, *awt = nullptr;
 };
 
 // What vba_schur_outlier_power needs beyond the reliability scratch, allocated by the first power query of a handle: its outputs on
-// the device (six figures per row, three per landmark, pose_fit [n][4], fit with the fourteen slots of vba_schur_outlier_power_dyn),
+// the device (six figures per row, three per landmark, pose_fit [n][4], fit with the seventeen slots of vba_schur_outlier_power_att),
 // pull [m] = |Sigma_il[0:3,:] z_l| of every row for the landmarks' maxima, and two timing events of its own.
 struct SchurPow {
     SchurScratch sc;
@@ -234,12 +235,16 @@ struct SchurAtt {
 };
 
 // why vba_schur_reliability_dyn, vba_schur_snoop_dyn and vba_schur_outlier_power_dyn refuse a handle with the attitude factor
+// (vba_schur_reliability_att, vba_schur_snoop_att and vba_schur_outlier_power_att are the queries of such a handle)
 constexpr char kAttRefusal[] = " is not available on a handle with the attitude factor: its redundancy counts and edge leverages do not "
                                "know the 3 (n - 1) attitude equations";
 
 // why the three queries refuse a handle with the dynamics factor (vba_schur_covariance_dyn is the covariance query of such a handle)
 constexpr char kDynRefusal[] = " is not available on a handle with the dynamics factor: its redundancy counts and gathers assume the "
                                "6 n reduced system of the reprojection rows";
+
+// which handle a body shared by three entries serves: the plain one, one with the dynamics factor, one with the attitude factor too
+enum SchurKind { kSchurPlain = 0, kSchurDyn = 1, kSchurAtt = 2 };
 
 struct vba_schur_context {
     int device = 0;
@@ -296,6 +301,14 @@ int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEv
 int schur_rel_alloc(vba_schur_handle h);
 int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
 int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
+int schur_rel_device_att(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
+// the device part of the reliability query of a handle of this kind
+inline int schur_rel_device_of(SchurKind kind, vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0) {
+    return kind == kSchurAtt ? schur_rel_device_att(h, lamda, ev_begin, V, bad, pow_ncp)
+         : kind == kSchurDyn ? schur_rel_device_dyn(h, lamda, ev_begin, V, bad, pow_ncp) : schur_rel_device(h, lamda, ev_begin, V, bad, pow_ncp);
+}
+// VBA_OK, or why an entry of this kind (`dyn_entry`: the name of its dynamics-only counterpart) does not serve this handle
+int schur_kind_check(SchurKind kind, vba_schur_handle h, const char* dyn_entry);
 
 // ---- vba_schur_power.hip
 // k_pow_rows on the handle's stream in the place of k_rel_rows (the power scratch is allocated): lev, wt, om of the reliability

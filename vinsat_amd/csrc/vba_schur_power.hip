@@ -1,4 +1,4 @@
-// vba_schur_power.hip -- the outlier power query of the free-landmark mode (vba_schur_outlier_power, vba_schur_outlier_power_dyn;
+// vba_schur_power.hip -- the outlier power query of the free-landmark mode (vba_schur_outlier_power, _dyn, _att;
 // include/vinsat_ba.h carries the contract, vba_schur.hip the map of the units): the device part of the reliability query of the
 // handle (vba_schur_rel.hip) with k_pow_rows in the place of k_rel_rows, so that the gather of Sigma_il -- the expensive part of a
 // row -- is formed once per row in this query, then the figures per landmark and per pose and the totals.  The row's gather and P_k
@@ -161,7 +161,7 @@ int schur_pow_alloc(vba_schur_handle h) {
     size_t o_row[7], o_lm[3];
     for (size_t& o : o_row) o = lay.need(m * 8);
     for (size_t& o : o_lm) o = lay.need(L * 8);
-    const size_t o_pf = lay.need(n * 32), o_fit = lay.need(14 * 8);
+    const size_t o_pf = lay.need(n * 32), o_fit = lay.need(17 * 8);
     if (int rc = schur_scratch_alloc(P.sc, lay.bytes, "outlier power scratch")) return rc;
     char* A = P.sc.arena;
     double** row[7] = {&P.mdb, &P.epos, &P.eatt, &P.elm, &P.dpos, &P.dlm, &P.pull};
@@ -171,17 +171,17 @@ int schur_pow_alloc(vba_schur_handle h) {
     return VBA_OK;
 }
 
-// The body of both entries (dyn: the handle has the dynamics factor and everything comes from the device part of
-// vba_schur_reliability_dyn; the three kernels are the same, the fit leads with that query's ten slots).
-int schur_power_call(vba_schur_handle h, bool dyn, double lamda, double ncp, double crit, double* mdb, double* ext_pos, double* ext_att,
+// The body of the three entries (kind: the handle has the dynamics factor, or the attitude factor too, and everything comes from
+// the device part of vba_schur_reliability_dyn / vba_schur_reliability_att; the three kernels are the same, the fit leads with that
+// query's ten / thirteen slots).
+int schur_power_call(vba_schur_handle h, SchurKind kind, double lamda, double ncp, double crit, double* mdb, double* ext_pos, double* ext_att,
                      double* ext_lm, double* del_pos, double* del_lm, double* lm_mdb, double* lm_ext, double* lm_del_pos, double* pose_fit,
                      double* fit, int* info) {
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!(ncp > 0.0 && ncp <= 1.79e308)) return sfail(VBA_EINVAL, "ncp must be positive and finite");
     if (!(crit > 0.0)) return sfail(VBA_EINVAL, "crit must be > 0 (+inf counts nothing)");
     if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    if (dyn && !h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
-    if (h->att.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_outlier_power_dyn") + kAttRefusal);
+    if (int rc = schur_kind_check(kind, h, "vba_schur_outlier_power_dyn")) return rc;
     SCHK(hipSetDevice(h->device));
     if (int rc = schur_query_alloc(h)) return rc;
     if (int rc = schur_query_index(h)) return rc;
@@ -192,10 +192,10 @@ int schur_power_call(vba_schur_handle h, bool dyn, double lamda, double ncp, dou
     hipStream_t s = h->stream;
     SchurView V;
     int bad = 0;
-    if (int rc = dyn ? schur_rel_device_dyn(h, lamda, P.sc.ev[0], V, &bad, ncp) : schur_rel_device(h, lamda, P.sc.ev[0], V, &bad, ncp)) return rc;
+    if (int rc = schur_rel_device_of(kind, h, lamda, P.sc.ev[0], V, &bad, ncp)) return rc;
     *info = bad;
     const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
-    const int lead = dyn ? 10 : 8;
+    const int lead = kind == kSchurAtt ? 13 : kind == kSchurDyn ? 10 : 8;
     struct Out { double* host; const double* dev; size_t count; };
     const Out outs[11] = {{mdb, P.mdb, m}, {ext_pos, P.epos, m}, {ext_att, P.eatt, m}, {ext_lm, P.elm, m}, {del_pos, P.dpos, m}, {del_lm, P.dlm, m},
                           {lm_mdb, P.lm_mdb, L}, {lm_ext, P.lm_ext, L}, {lm_del_pos, P.lm_del, L}, {pose_fit, P.pose_fit, 4 * n},
@@ -233,7 +233,7 @@ int vba_schur_outlier_power(vba_schur_handle h, double lamda, double ncp, double
                             int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
     if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_outlier_power") + kDynRefusal);
-    return schur_power_call(h, false, lamda, ncp, crit, mdb, ext_pos, ext_att, ext_lm, del_pos, del_lm, lm_mdb, lm_ext, lm_del_pos, pose_fit, fit, info);
+    return schur_power_call(h, kSchurPlain, lamda, ncp, crit, mdb, ext_pos, ext_att, ext_lm, del_pos, del_lm, lm_mdb, lm_ext, lm_del_pos, pose_fit, fit, info);
 }
 
 int vba_schur_last_outlier_power_ms(vba_schur_handle h, float* ms) {
@@ -246,10 +246,23 @@ int vba_schur_outlier_power_dyn(vba_schur_handle h, double lamda, double ncp, do
                                 double* ext_lm, double* del_pos, double* del_lm, double* lm_mdb, double* lm_ext, double* lm_del_pos, double* pose_fit,
                                 double* fit, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    return schur_power_call(h, true, lamda, ncp, crit, mdb, ext_pos, ext_att, ext_lm, del_pos, del_lm, lm_mdb, lm_ext, lm_del_pos, pose_fit, fit, info);
+    return schur_power_call(h, kSchurDyn, lamda, ncp, crit, mdb, ext_pos, ext_att, ext_lm, del_pos, del_lm, lm_mdb, lm_ext, lm_del_pos, pose_fit, fit, info);
 }
 
 int vba_schur_last_outlier_power_dyn_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->pow.sc.ms;
+    return VBA_OK;
+}
+
+int vba_schur_outlier_power_att(vba_schur_handle h, double lamda, double ncp, double crit, double* mdb, double* ext_pos, double* ext_att,
+                                double* ext_lm, double* del_pos, double* del_lm, double* lm_mdb, double* lm_ext, double* lm_del_pos, double* pose_fit,
+                                double* fit, int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    return schur_power_call(h, kSchurAtt, lamda, ncp, crit, mdb, ext_pos, ext_att, ext_lm, del_pos, del_lm, lm_mdb, lm_ext, lm_del_pos, pose_fit, fit, info);
+}
+
+int vba_schur_last_outlier_power_att_ms(vba_schur_handle h, float* ms) {
     if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
     *ms = h->pow.sc.ms;
     return VBA_OK;

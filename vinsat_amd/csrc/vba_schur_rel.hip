@@ -6,7 +6,11 @@
 // part is what vba_schur_snoop_dyn starts with.  vba_schur.hip carries the map of the units; the closed forms are
 // vba_schur_rel_math.h and vba_schur_dyn_rel.h; the gather of a row is vba_schur_rowpass.h, shared with the row pass of the outlier
 // power query (vba_schur_power.hip), which takes the place of k_rel_rows in the device part when that query runs it.
+// vba_schur_reliability_att, the query of a handle with the attitude factor too, follows vba_schur_reliability_dyn in the same way:
+// its launches in their order, then leverage and w-test of every attitude edge (vba_schur_att_rel.h) and the edges' share of the fit;
+// its device part is what vba_schur_snoop_att and vba_schur_outlier_power_att start with.
 #include "vba_schur_context.h"
+#include "vba_schur_att_rel.h"
 #include "vba_schur_dyn_rel.h"
 #include "vba_schur_rel_math.h"
 #include "vba_schur_rowpass.h"
@@ -165,7 +169,67 @@ __global__ __launch_bounds__(256) void k_rel_edge_totals(int n, int L, const dou
     }
 }
 
+// ------------------------------------------------------------------------------------------------ with the attitude factor
+// vba_schur_reliability_att, after the device part of vba_schur_reliability_dyn on a handle with both factors (state and edge blocks
+// of the Sigma that includes the attitude factor, a and J of the query's own build resident).
+//
+// Attitude edge, THREAD PER EDGE (vba_schur_att_rel.h): Sigma6 out of the attitude components of the three 9x9 blocks, P_a, its
+// trace, the w-test.  Not the lane group of k_rel_edges: an edge is 36 + 18 + 3 independent loads and 162 fma, which one lane holds
+// in registers without scratch (DESIGN 9.10 has the compiler's figures), and the w-test needs all of P_a in one lane -- a group of
+// three lanes would exchange nine entries by __shfl to save a chain of fma a fraction of a microsecond long.  There are n - 1 edges:
+// the kernel is a chain of dependent loads and fma, not a bandwidth matter.
+__global__ __launch_bounds__(256) void k_rel_att_edges(int n, double sigma, const double* J, const double* a, const double* state, const double* edge,
+                                                       double* alev, double* awt) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n - 1) return;
+    double P[9];
+    schur_att_rel_P(J + (size_t)e * 18, state + (size_t)e * 81, edge + (size_t)e * 81, state + (size_t)(e + 1) * 81, sigma, P);
+    const double av[3] = {a[(size_t)e * 3], a[(size_t)e * 3 + 1], a[(size_t)e * 3 + 2]};
+    alev[e] = schur_att_rel_leverage(P);
+    awt[e] = schur_att_rel_wtest(P, av, sigma);
+}
+
+// Behind k_rel_edge_totals, ONE block with its strided sum and tree (thread t takes the edges t, t + 256, ...): the attitude edges'
+// leverages, cost shares and largest finite w-test, folded into the fit k_rel_edge_totals left: Omega and the redundancy gain the
+// attitude edges, s0sq follows, fit[10] = t_att, fit[11] = Omega_att, fit[12] = largest finite att_wtest.
+__global__ __launch_bounds__(256) void k_rel_att_totals(int n, int L, const double* alev, const double* aom, const double* awt, double* fit) {
+    __shared__ double red[3][256];
+    const int t = threadIdx.x;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int e = t; e < n - 1; e += 256) {
+        a0 += alev[e];
+        a1 += aom[e];
+        const double x = awt[e];
+        if (x <= 1.79e308 && x > a2) a2 = x;    // (NaN fails both)
+    }
+    red[0][t] = a0; red[1][t] = a1; red[2][t] = a2;
+    for (int o = 128; o > 0; o >>= 1) {
+        __syncthreads();
+        if (t < o) {
+            red[0][t] += red[0][t + o];
+            red[1][t] += red[1][t + o];
+            const double x = red[2][t], y = red[2][t + o];
+            red[2][t] = y > x ? y : x;
+        }
+    }
+    if (t == 0) {
+        const double tatt = red[0][0], omatt = red[1][0];
+        const double Omega = fit[0] + omatt, meff = fit[1], trows = fit[2], tprior = fit[3], tedges = fit[8];
+        const double rho = ((((((2.0 * meff + 3.0 * (double)L) + 6.0 * (double)(n - 1)) + 3.0 * (double)(n - 1)) - trows) - tprior) - tedges) - tatt;
+        fit[0] = Omega; fit[4] = rho;
+        fit[5] = rho > 0.0 ? Omega / rho : __builtin_nan("");
+        fit[10] = tatt; fit[11] = omatt; fit[12] = red[2][0];
+    }
+}
+
 }  // namespace
+
+int schur_kind_check(SchurKind kind, vba_schur_handle h, const char* dyn_entry) {
+    if (kind != kSchurPlain && !h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
+    if (kind == kSchurAtt && !h->att.enabled) return sfail(VBA_ESTATE, "the attitude factor is not enabled on this handle");
+    if (kind != kSchurAtt && h->att.enabled) return sfail(VBA_ESTATE, std::string(dyn_entry) + kAttRefusal);
+    return VBA_OK;
+}
 
 // first reliability query of a handle: its scratch and its two timing events
 int schur_rel_alloc(vba_schur_handle h) {
@@ -175,13 +239,15 @@ int schur_rel_alloc(vba_schur_handle h) {
     const size_t m = (size_t)V.m, L = (size_t)V.L;
     SchurLayout lay;
     const size_t o_lev = lay.need(m * 8), o_wt = lay.need(m * 8), o_om = lay.need(m * 8), o_ll = lay.need(L * 8), o_lw = lay.need(L * 8),
-                 o_lo = lay.need(L * 8), o_ls = lay.need(L * 24), o_ps = lay.need((size_t)V.n * 24), o_fit = lay.need(80),
-                 o_el = lay.need(h->dyn.enabled ? ((size_t)V.n - 1) * 8 : 0);
+                 o_lo = lay.need(L * 8), o_ls = lay.need(L * 24), o_ps = lay.need((size_t)V.n * 24), o_fit = lay.need(13 * 8),
+                 o_el = lay.need(h->dyn.enabled ? ((size_t)V.n - 1) * 8 : 0), o_al = lay.need(h->att.enabled ? ((size_t)V.n - 1) * 8 : 0),
+                 o_aw = lay.need(h->att.enabled ? ((size_t)V.n - 1) * 8 : 0);
     if (int rc = schur_scratch_alloc(R.sc, lay.bytes, "reliability scratch")) return rc;
     char* A = R.sc.arena;
     R.lev = (double*)(A + o_lev); R.wt = (double*)(A + o_wt); R.om = (double*)(A + o_om); R.lmlev = (double*)(A + o_ll); R.lmwt = (double*)(A + o_lw);
     R.lmom = (double*)(A + o_lo); R.lm_stats = (double*)(A + o_ls); R.pose_stats = (double*)(A + o_ps); R.fit = (double*)(A + o_fit);
     if (h->dyn.enabled) R.elev = (double*)(A + o_el);
+    if (h->att.enabled) { R.alev = (double*)(A + o_al); R.awt = (double*)(A + o_aw); }
     return VBA_OK;
 }
 
@@ -224,7 +290,63 @@ int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, 
     return VBA_OK;
 }
 
+// The device part of vba_schur_reliability_att, shared with vba_schur_snoop_att and vba_schur_outlier_power_att:
+// schur_rel_device_dyn's launches in their order (on a handle with the attitude factor the covariance query's build includes it and
+// fills att.q_a, att.q_J, att.q_ecost), then the attitude edge pass and the attitude edges folded into the fit.  pow_ncp as in
+// schur_rel_device.
+int schur_rel_device_att(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp) {
+    SchurQuery& Q = h->q;
+    SchurRel& R = h->rel;
+    hipStream_t s = h->stream;
+    if (int rc = schur_rel_device_dyn(h, lamda, ev_begin, V, bad, pow_ncp)) return rc;
+    if (*bad != 0) return VBA_OK;
+    hipLaunchKernelGGL(k_rel_att_edges, dim3((V.n - 1 + 255) / 256), dim3(256), 0, s, V.n, h->att.sigma, h->att.q_J, h->att.q_a, Q.state, Q.edge, R.alev,
+                       R.awt);
+    hipLaunchKernelGGL(k_rel_att_totals, dim3(1), dim3(256), 0, s, V.n, V.L, R.alev, h->att.q_ecost, R.awt, R.fit);
+    return VBA_OK;
+}
+
 extern "C" {
+
+int vba_schur_reliability_att(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
+                              double* lm_stats, double* pose_stats, double* edge_leverage, double* edge_omega, double* att_leverage,
+                              double* att_wtest, double* att_omega, double* fit, int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    if (int rc = schur_kind_check(kSchurAtt, h, "vba_schur_reliability_dyn")) return rc;
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    if (int rc = schur_query_index(h)) return rc;
+    if (int rc = schur_rel_alloc(h)) return rc;
+    SchurRel& R = h->rel;
+    hipStream_t s = h->stream;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_rel_device_att(h, lamda, R.sc.ev[0], V, &bad)) return rc;
+    *info = bad;
+    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
+    struct Out { double* host; const double* dev; size_t count; };
+    const Out outs[12] = {{leverage, R.lev, m}, {wtest, R.wt, m}, {lm_leverage, R.lmlev, L}, {lm_wtest, R.lmwt, L}, {lm_stats, R.lm_stats, 3 * L},
+                          {pose_stats, R.pose_stats, 3 * n}, {edge_leverage, R.elev, n - 1}, {edge_omega, h->q.dyn_ecost, n - 1},
+                          {att_leverage, R.alev, n - 1}, {att_wtest, R.awt, n - 1}, {att_omega, h->att.q_ecost, n - 1}, {fit, R.fit, 13}};
+    if (bad != 0) {                 // no factor, no covariance, no test: NaN, and the row in *info
+        if (int rc = schur_scratch_finish(R.sc, s)) return rc;
+        for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
+        return VBA_OK;
+    }
+    return schur_scratch_finish(R.sc, s, [&]() -> int {
+        SCHK(hipGetLastError());
+        for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
+        return VBA_OK;
+    });
+}
+
+int vba_schur_last_reliability_att_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->rel.sc.ms;
+    return VBA_OK;
+}
 
 int vba_schur_reliability_dyn(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
                               double* lm_stats, double* pose_stats, double* edge_leverage, double* edge_omega, double* fit, int* info) {

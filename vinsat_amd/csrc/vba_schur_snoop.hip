@@ -1,4 +1,4 @@
-// vba_schur_snoop.hip -- free-landmark data snooping (vba_schur_snoop, vba_schur_snoop_dyn, vba_schur_rejected, vba_schur_snoop_restore;
+// vba_schur_snoop.hip -- free-landmark data snooping (vba_schur_snoop, vba_schur_snoop_dyn, vba_schur_snoop_att, vba_schur_rejected, vba_schur_snoop_restore;
 // include/vinsat_ba.h carries the contract, vba_schur_context.h the handle, vba_schur.hip the map of the units): its passes, then the
 // entry points.  The passes run behind the device part of vba_schur_reliability (of vba_schur_reliability_dyn on a handle with the
 // dynamics factor: the same passes on the same scratch) on the handle's
@@ -161,16 +161,16 @@ static SchurSnoopView schur_snoop_view(vba_schur_handle h) {
     return W;
 }
 
-// The body of vba_schur_snoop and of vba_schur_snoop_dyn (dyn: the handle has the dynamics factor and the tests come from the device
-// part of vba_schur_reliability_dyn; the passes, the masks and the saved weights are the same -- edges are never rejected).
-static int schur_snoop_call(vba_schur_handle h, bool dyn, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts,
+// The body of vba_schur_snoop, vba_schur_snoop_dyn and vba_schur_snoop_att (kind: the handle has the dynamics factor, or the attitude
+// factor too, and the tests come from the device part of vba_schur_reliability_dyn / vba_schur_reliability_att; the passes, the masks
+// and the saved weights are the same -- edges of either kind are never rejected).
+static int schur_snoop_call(vba_schur_handle h, SchurKind kind, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts,
                             double* crit_used, int* info) {
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!(crit >= 0.0)) return sfail(VBA_EINVAL, "crit must be >= 0 (+inf rejects nothing)");
     if (min_rows < 0 || min_track < 0) return sfail(VBA_EINVAL, "min_rows and min_track must be >= 0");
     if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    if (dyn && !h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
-    if (h->att.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_snoop_dyn") + kAttRefusal);
+    if (int rc = schur_kind_check(kind, h, "vba_schur_snoop_dyn")) return rc;
     SCHK(hipSetDevice(h->device));
     if (int rc = schur_query_alloc(h)) return rc;
     if (int rc = schur_query_index(h)) return rc;
@@ -180,7 +180,7 @@ static int schur_snoop_call(vba_schur_handle h, bool dyn, double lamda, double c
     hipStream_t s = h->stream;
     SchurView V;
     int bad = 0;
-    if (int rc = dyn ? schur_rel_device_dyn(h, lamda, Z.sc.ev[0], V, &bad) : schur_rel_device(h, lamda, Z.sc.ev[0], V, &bad)) return rc;
+    if (int rc = schur_rel_device_of(kind, h, lamda, Z.sc.ev[0], V, &bad)) return rc;
     *info = bad;
     if (counts) counts[0] = counts[1] = counts[2] = 0;
     if (bad != 0) {                 // no factor, no test: nothing is rejected; the critical value of a fit that does not exist
@@ -223,16 +223,28 @@ int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, i
                     int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
     if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_snoop") + kDynRefusal);
-    return schur_snoop_call(h, false, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
+    return schur_snoop_call(h, kSchurPlain, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
 }
 
 int vba_schur_snoop_dyn(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
                         int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    return schur_snoop_call(h, true, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
+    return schur_snoop_call(h, kSchurDyn, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
 }
 
 int vba_schur_last_snoop_dyn_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->snoop.sc.ms;
+    return VBA_OK;
+}
+
+int vba_schur_snoop_att(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
+                        int* info) {
+    if (!h || !info) return sfail(VBA_EINVAL, "null argument");
+    return schur_snoop_call(h, kSchurAtt, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
+}
+
+int vba_schur_last_snoop_att_ms(vba_schur_handle h, float* ms) {
     if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
     *ms = h->snoop.sc.ms;
     return VBA_OK;

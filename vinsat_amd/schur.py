@@ -28,7 +28,9 @@ from ._lib import PD
 FIT_NAMES = ("omega", "m_eff", "t_rows", "t_prior", "rho", "s0sq", "max_wtest", "max_lm_wtest")
 # fit[10] of vba_schur_reliability_dyn: the same eight, then the edges' share of the traces and of the cost
 FIT_NAMES_DYN = FIT_NAMES + ("t_edges", "omega_edges")
-# the four slots vba_schur_outlier_power(_dyn) puts behind the fit of the reliability query, and its arrays in the order of the entry
+# fit[13] of vba_schur_reliability_att: the same ten, then the attitude edges' share of the traces and of the cost and their largest test
+FIT_NAMES_ATT = FIT_NAMES_DYN + ("t_att", "omega_att", "max_att_wtest")
+# the four slots vba_schur_outlier_power(_dyn, _att) puts behind the fit of the reliability query, and its arrays in the order of the entry
 POWER_FIT_NAMES = ("n_rows_over_crit", "max_ext_pos", "n_lm_over_crit", "max_lm_del_pos")
 POWER_ROW_KEYS = ("mdb", "ext_pos", "ext_att", "ext_lm", "del_pos", "del_lm")
 POWER_LM_KEYS = ("lm_mdb", "lm_ext", "lm_del_pos")
@@ -427,17 +429,23 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_snoop_dyn_ms(self.h, byref(v)))
         return v.value
 
-    def _outlier_power(self, dyn, lamda, ncp, crit, strict):
-        names = FIT_NAMES_DYN + POWER_FIT_NAMES if dyn else FIT_NAMES + POWER_FIT_NAMES
+    # kind of handle -> (leading fit names, entry, label of the error message) of the outlier power query
+    _POWER_KINDS = {"plain": (FIT_NAMES, "vba_schur_outlier_power", ""), "state": (FIT_NAMES_DYN, "vba_schur_outlier_power_dyn", "state "),
+                    "attitude": (FIT_NAMES_ATT, "vba_schur_outlier_power_att", "attitude ")}
+
+    def _outlier_power(self, kind, lamda, ncp, crit, strict):
+        """``kind``: a key of ``_POWER_KINDS`` -- the plain handle, one with the dynamics factor, one with the attitude factor too."""
+        lead, entry_name, label = self._POWER_KINDS[kind]
+        names = lead + POWER_FIT_NAMES
         out = {k: np.empty(self.m) for k in POWER_ROW_KEYS}
         out.update({k: np.empty(self.L) for k in POWER_LM_KEYS})
         out["pose_fit"] = np.empty((self.n, 4))
         fit, info = np.empty(len(names)), c_int()
-        entry = self.lib.vba_schur_outlier_power_dyn if dyn else self.lib.vba_schur_outlier_power
+        entry = getattr(self.lib, entry_name)
         self._check(entry(self.h, float(lamda), float(ncp), float(crit), *[a.ctypes.data_as(PD) for a in out.values()], fit.ctypes.data_as(PD),
                           byref(info)))
         if info.value != 0 and strict:
-            raise _lib.VbaError(f"schur {'state ' if dyn else ''}outlier power: the reduced system is not positive definite at lamda = {lamda:g} "
+            raise _lib.VbaError(f"schur {label}outlier power: the reduced system is not positive definite at lamda = {lamda:g} "
                                 f"(non-positive pivot at row {info.value - 1})")
         for key in POWER_ROW_KEYS:                      # device rows are sorted by landmark: back to the caller's order
             back = np.empty(self.m)
@@ -459,7 +467,7 @@ class SchurBA:
         the chosen power.  Up to the variance factor of the weights (:func:`scaled_power`).  Nothing on the handle changes.
 
         ``strict`` as in :meth:`reliability`."""
-        return self._outlier_power(False, lamda, ncp, crit, strict)
+        return self._outlier_power("plain", lamda, ncp, crit, strict)
 
     def last_outlier_power_ms(self):
         v = c_float()
@@ -470,11 +478,74 @@ class SchurBA:
         """``vba_schur_outlier_power_dyn``: the dict of :meth:`outlier_power` on a handle with the dynamics factor, every figure from
         the covariance of the system WITH the factor; ``fit`` is a dict of :data:`FIT_NAMES_DYN` then :data:`POWER_FIT_NAMES`.  There
         is no figure in velocity and none for an edge (the header says why).  A handle without the factor raises."""
-        return self._outlier_power(True, lamda, ncp, crit, strict)
+        return self._outlier_power("state", lamda, ncp, crit, strict)
 
     def last_state_outlier_power_ms(self):
         v = c_float()
         self._check(self.lib.vba_schur_last_outlier_power_dyn_ms(self.h, byref(v)))
+        return v.value
+
+    def attitude_reliability(self, lamda=0.0, strict=True):
+        """``vba_schur_reliability_att`` at the resident state of a handle with the dynamics AND the attitude factor
+        (``include/vinsat_ba.h``): the dict of :meth:`state_reliability` -- every leverage and test from the covariance of the system
+        with BOTH factors -- plus ``att_leverage [n-1]`` (trace of the attitude edge's 3x3 block of the hat matrix, in ``(0, 3]``),
+        ``att_wtest [n-1]`` (the test of the gyro's gap rotation ``i -> i + 1``; NaN where ``I - P_a`` is not positive definite) and
+        ``att_omega [n-1]`` (``sigma_att |a|^2``); ``fit`` is a dict of :data:`FIT_NAMES_ATT`, its ``rho`` and ``omega`` count the
+        edges of both kinds.  There is still no w-test of an orbit edge.  :func:`suspects` reads the dict unchanged,
+        :func:`gyro_suspects` reads ``att_wtest``.  Nothing on the handle changes.
+
+        ``strict`` as in :meth:`state_covariance`.  A handle without the attitude factor raises: :meth:`state_reliability` or
+        :meth:`reliability` is its query."""
+        ne = max(self.n - 1, 0)
+        out = dict(leverage=np.empty(self.m), wtest=np.empty(self.m), lm_leverage=np.empty(self.L), lm_wtest=np.empty(self.L),
+                   lm_stats=np.empty((self.L, 3)), pose_stats=np.empty((self.n, 3)), edge_leverage=np.empty(ne), edge_omega=np.empty(ne),
+                   att_leverage=np.empty(ne), att_wtest=np.empty(ne), att_omega=np.empty(ne))
+        fit, info = np.empty(len(FIT_NAMES_ATT)), c_int()
+        self._check(self.lib.vba_schur_reliability_att(self.h, float(lamda), *[a.ctypes.data_as(PD) for a in out.values()],
+                                                       fit.ctypes.data_as(PD), byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur attitude reliability: the reduced system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        for key in ("leverage", "wtest"):               # device rows are sorted by landmark: back to the caller's order
+            back = np.empty(self.m)
+            back[self.order] = out[key]
+            out[key] = back
+        out["fit"] = dict(zip(FIT_NAMES_ATT, fit.tolist()))
+        out["info"] = info.value
+        return out
+
+    def last_attitude_reliability_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_reliability_att_ms(self.h, byref(v)))
+        return v.value
+
+    def attitude_snoop(self, lamda=0.0, crit=3.29, scaled=True, min_rows=6, min_track=3, strict=True):
+        """``vba_schur_snoop_att``: :meth:`snoop` on a handle with both factors -- the same rule, arguments and result, fed by the
+        device part of :meth:`attitude_reliability` (``scaled`` reads its ``s0sq``, which counts the attitude equations).  Edges of
+        either kind are never rejected: a gyro suspect is reported (:func:`gyro_suspects`), not acted on.  :meth:`rejected` and
+        :meth:`restore_rejected` serve it too."""
+        counts, used, info = (c_int * 3)(), c_double(), c_int()
+        self._check(self.lib.vba_schur_snoop_att(self.h, float(lamda), float(crit), int(bool(scaled)), int(min_rows), int(min_track), counts,
+                                                 byref(used), byref(info)))
+        if info.value != 0 and strict:
+            raise _lib.VbaError(f"schur attitude snoop: the reduced system is not positive definite at lamda = {lamda:g} "
+                                f"(non-positive pivot at row {info.value - 1})")
+        return dict(rows=counts[0], landmarks=counts[1], rows_via_landmarks=counts[2], crit_used=used.value, info=info.value)
+
+    def last_attitude_snoop_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_snoop_att_ms(self.h, byref(v)))
+        return v.value
+
+    def attitude_outlier_power(self, lamda=0.0, ncp=17.075, crit=3.29, strict=True):
+        """``vba_schur_outlier_power_att``: the dict of :meth:`outlier_power` on a handle with both factors, every figure from the
+        covariance of the system with both; ``fit`` is a dict of :data:`FIT_NAMES_ATT` then :data:`POWER_FIT_NAMES`.  There is no
+        figure for an edge of either kind.  A handle without the attitude factor raises."""
+        return self._outlier_power("attitude", lamda, ncp, crit, strict)
+
+    def last_attitude_outlier_power_ms(self):
+        v = c_float()
+        self._check(self.lib.vba_schur_last_outlier_power_att_ms(self.h, byref(v)))
         return v.value
 
     def reweight(self, alpha):
@@ -506,7 +577,7 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_reweight_ms(self.h, byref(v)))
         return v.value
 
-    def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10, snoop=None, robust=None, state_snoop=None):
+    def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10, snoop=None, robust=None, state_snoop=None, attitude_snoop=None):
         """Levenberg-Marquardt driver: damping x10 on a rejected trial, /10 on an accepted one.  Returns the cost history.
 
         ``robust = dict(outer=8, alpha=None)`` (any subset) replaces the single LM loop by the robust loop: for ``it`` in
@@ -519,9 +590,11 @@ class SchurBA:
         after the loop ends, at most ``rounds`` rounds of :meth:`snoop`; a round that rejected something is followed by the LM loop again from the
         resident state, one that rejected nothing ends the rounds.  The history gains one entry per round, ``("snoop", dict of
         :meth:`snoop`)``.  ``state_snoop = dict(...)`` is the same with :meth:`state_snoop`, the snoop of a handle with the dynamics
-        factor (``snoop=`` on such a handle raises as :meth:`snoop` does); give one of the two."""
-        if snoop is not None and state_snoop is not None:
-            raise ValueError("snoop and state_snoop are the rounds of two kinds of handle: give one of them")
+        factor (``snoop=`` on such a handle raises as :meth:`snoop` does), ``attitude_snoop = dict(...)`` the same with
+        :meth:`attitude_snoop`, the snoop of a handle with the attitude factor too; give one of the three."""
+        given = [(k, o) for k, o in (("snoop", snoop), ("state_snoop", state_snoop), ("attitude_snoop", attitude_snoop)) if o is not None]
+        if len(given) > 1:
+            raise ValueError("snoop, state_snoop and attitude_snoop are the rounds of three kinds of handle: give one of them")
         if robust is None:
             hist = self._lm_loop(lamda0, max_iters, tol)
         else:
@@ -536,10 +609,10 @@ class SchurBA:
                 if res["status"] != 0:
                     break
                 hist += self._lm_loop(lamda0, max_iters, tol)
-        if snoop is None and state_snoop is None:
+        if not given:
             return hist
-        opts = dict(snoop if state_snoop is None else state_snoop)
-        one_round = self.snoop if state_snoop is None else self.state_snoop
+        opts = dict(given[0][1])
+        one_round = getattr(self, given[0][0])
         rounds = int(opts.pop("rounds", 8))
         for _ in range(rounds):
             res = one_round(**opts)
@@ -572,6 +645,16 @@ def suspects(rel, crit, scaled=False):
     thr = float(crit) * (np.sqrt(rel["fit"]["s0sq"]) if scaled else 1.0)
     with np.errstate(invalid="ignore"):
         return np.nonzero(rel["wtest"] > thr)[0], np.nonzero(rel["lm_wtest"] > thr)[0]
+
+
+def gyro_suspects(rel, crit, scaled=False):
+    """The indices (ascending) of the attitude edges ``i -> i + 1`` whose ``att_wtest`` exceeds ``crit`` in the dict of
+    :meth:`SchurBA.attitude_reliability` -- ``crit * sqrt(s0sq)`` with ``scaled``, i.e. the test divided by ``s0``.  NaN tests exceed
+    nothing.  A suspect is a gap whose gyro rotation the window contradicts; the edges next to it absorb part of the fault and rank
+    behind it."""
+    thr = float(crit) * (np.sqrt(rel["fit"]["s0sq"]) if scaled else 1.0)
+    with np.errstate(invalid="ignore"):
+        return np.nonzero(rel["att_wtest"] > thr)[0]
 
 
 def scaled_power(power):
