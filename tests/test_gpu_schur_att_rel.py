@@ -6,6 +6,7 @@ before it is asserted.  Device against reference, measured on an MI355X: DESIGN 
 without the feature does not have.
 """
 import ctypes
+import functools
 import itertools
 
 import numpy as np
@@ -13,37 +14,13 @@ import pytest
 
 import schur_att_rel_cases as T
 import schur_power_cases as PW
+import schur_query_harness as H
 
 pytestmark = pytest.mark.gpu
-EPS = np.finfo(np.float64).eps
-OUTPUTS = ("leverage", "wtest", "lm_leverage", "lm_wtest", "lm_stats", "pose_stats", "edge_leverage", "edge_omega", "att_leverage", "att_wtest",
-           "att_omega", "fit")
+OUTPUTS = H.REL_OUTPUTS["att"]
 NCP = PW.NCP
-
-
-def engine(d, attitude=True, dynamics=True, sigma_att=None, state=None, w=None):
-    from vinsat_amd.schur import SchurBA
-    kw = dict(time_idx=d["time_idx"], sigma_dyn=d["sigma_dyn"]) if dynamics else {}
-    if attitude:
-        kw.update(cumrot=d["cumrot"], sigma_att=d["sigma_att"] if sigma_att is None else sigma_att)
-    e = SchurBA(d["states0"], d["X0"], d["uv"], d["w"] if w is None else w, d["pose_of_row"], d["landmark_of_row"], d["intrinsics"],
-                sigma_prior=d["sigma"], **kw)
-    e.set_state(*(state or (d["states0"], d["Xs"])))
-    return e
-
-
-def _fitv(rel):
-    return np.array(list(rel["fit"].values()))
-
-
-def _same(a, b):
-    """Bitwise equal dicts of ``SchurBA.attitude_reliability`` (NaN equal to NaN)."""
-    return all(np.array_equal(a[k], b[k], equal_nan=True) for k in OUTPUTS[:-1]) and np.array_equal(_fitv(a), _fitv(b), equal_nan=True) and \
-        a["info"] == b["info"]
-
-
-def _same_cov(a, b):
-    return all(np.array_equal(a[k], b[k]) for k in ("state", "edges", "landmark"))
+engine = functools.partial(H.engine, dynamics=True, attitude=True)
+_fitv, _same, _same_cov, _raw = H._fitv, H._same(OUTPUTS), H._same_cov, functools.partial(H._raw, "att")
 
 
 # ------------------------------------------------------------------------------------------------ 1. accuracy, device identity
@@ -65,27 +42,8 @@ def test_matches_the_reference(name, lam):
     assert np.all(got["att_leverage"] > 0.0) and np.all(got["att_leverage"] <= 3.0)
     assert T.rel(got["edge_omega"], r.edge_omega) <= 1e-10 and T.rel(got["att_omega"], r.att_omega) <= 1e-10   # (cost shares)
     assert om <= 1e-12
-    # statistics and totals: against the reference, and against the device's own arrays (maxima and counts exactly)
-    w = d["w"]
-    for key, index, size in (("lm_stats", d["landmark_of_row"], e.L), ("pose_stats", d["pose_of_row"], e.n)):
-        own = T.stats_of(got["leverage"], got["wtest"], w, index, size)
-        assert np.abs(got[key][:, 0] - own[:, 0]).max() <= np.bincount(index).max() * EPS * np.abs(own[:, 0]).max()
-        assert np.array_equal(got[key][:, 1:], own[:, 1:])
-        ref = getattr(r, key)
-        assert T.rel(got[key][:, 0], ref[:, 0]) <= T.bar(r, "leverage") and T.rel(got[key][:, 1], ref[:, 1]) <= T.bar(r, "wtest")
-    fin = lambda a: float(np.max(a[np.isfinite(a)], initial=0.0))
-    assert fit["m_eff"] == r.fit["m_eff"] == float((w > 0).sum())
-    assert fit["max_wtest"] == fin(got["wtest"]) and fit["max_lm_wtest"] == fin(got["lm_wtest"]) and fit["max_att_wtest"] == fin(got["att_wtest"])
     ne = e.n - 1
-    for k, own, cnt in (("t_rows", got["leverage"], e.m), ("t_prior", got["lm_leverage"], e.L), ("t_edges", got["edge_leverage"], ne),
-                        ("omega_edges", got["edge_omega"], ne), ("t_att", got["att_leverage"], ne), ("omega_att", got["att_omega"], ne)):
-        assert abs(fit[k] - own.sum()) <= cnt * EPS * abs(fit[k]), k
-    assert fit["rho"] == ((((((2.0 * fit["m_eff"] + 3.0 * e.L) + 6.0 * ne) + 3.0 * ne) - fit["t_rows"]) - fit["t_prior"]) - fit["t_edges"]) - fit["t_att"]
-    assert fit["s0sq"] == fit["omega"] / fit["rho"]
-    for k, fam, cnt, top in (("t_rows", "leverage", e.m, r.leverage.max()), ("t_prior", "lm_leverage", e.L, r.lm_leverage.max()),
-                             ("t_edges", "edge_leverage", ne, r.edge_leverage.max()), ("t_att", "att_leverage", ne, r.att_leverage.max())):
-        assert abs(fit[k] - r.fit[k]) <= cnt * top * T.bar(r, fam), k
-    assert abs(fit["rho"] - r.fit["rho"]) <= 1e-9 * r.unknowns and abs(fit["s0sq"] - r.fit["s0sq"]) <= 1e-9 * r.fit["s0sq"]
+    H.statistics_and_totals("att", T, d, e, got, r)
     # the trace identity from the device's own outputs
     c = e.state_covariance(lam)
     trace = np.trace(c["state"], axis1=1, axis2=2).sum() + np.trace(c["landmark"], axis1=1, axis2=2).sum()
@@ -118,17 +76,6 @@ def test_empty_pose_window_is_answered_at_zero_damping():
 
 
 # ------------------------------------------------------------------------------------------------ 3. bits
-def _raw(e, lam, on=(True,) * 12):
-    """The C entry itself: (rc, info, outputs in the order of OUTPUTS, device row order); outputs not asked for are None (NULL)."""
-    from vinsat_amd._lib import PD
-    ne = e.n - 1
-    shapes = ((e.m,), (e.m,), (e.L,), (e.L,), (e.L, 3), (e.n, 3), (ne,), (ne,), (ne,), (ne,), (ne,), (13,))
-    bufs = [np.full(s, 7.0) if o else None for s, o in zip(shapes, on)]
-    info = ctypes.c_int(-1)
-    rc = e.lib.vba_schur_reliability_att(e.h, float(lam), *[b.ctypes.data_as(PD) if b is not None else None for b in bufs], ctypes.byref(info))
-    return (rc, info.value, *bufs)
-
-
 def test_second_query_second_handle_and_null_outputs_give_the_same_bits():
     d = T.case("29")
     e, f = engine(d), engine(d)

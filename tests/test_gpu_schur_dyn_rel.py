@@ -5,6 +5,7 @@ PARITY UNPINNED as the rest of the add-on.  Every figure is printed before it is
 an MI355X: DESIGN 9.7.
 """
 import ctypes
+import functools
 import itertools
 
 import numpy as np
@@ -13,33 +14,12 @@ import pytest
 import schur_cases as SC
 import schur_dyn_cov_cases as V
 import schur_dyn_rel_cases as Q
+import schur_query_harness as H
 
 pytestmark = pytest.mark.gpu
-EPS = np.finfo(np.float64).eps
-OUTPUTS = ("leverage", "wtest", "lm_leverage", "lm_wtest", "lm_stats", "pose_stats", "edge_leverage", "edge_omega", "fit")
-
-
-def engine(d, dynamics=True, sigma_dyn=None, state=None, w=None):
-    from vinsat_amd.schur import SchurBA
-    kw = dict(time_idx=d["time_idx"], sigma_dyn=d["sigma_dyn"] if sigma_dyn is None else sigma_dyn) if dynamics else {}
-    e = SchurBA(d["states0"], d["X0"], d["uv"], d["w"] if w is None else w, d["pose_of_row"], d["landmark_of_row"], d["intrinsics"],
-                sigma_prior=d["sigma"], **kw)
-    e.set_state(*(state or (d["states0"], d["Xs"])))
-    return e
-
-
-def _fitv(rel):
-    return np.array(list(rel["fit"].values()))
-
-
-def _same(a, b):
-    """Bitwise equal dicts of ``SchurBA.state_reliability`` (NaN equal to NaN)."""
-    return all(np.array_equal(a[k], b[k], equal_nan=True) for k in OUTPUTS[:-1]) and np.array_equal(_fitv(a), _fitv(b), equal_nan=True) and \
-        a["info"] == b["info"]
-
-
-def _same_cov(a, b):
-    return all(np.array_equal(a[k], b[k]) for k in ("state", "edges", "landmark"))
+OUTPUTS = H.REL_OUTPUTS["dyn"]
+engine = functools.partial(H.engine, dynamics=True)
+_fitv, _same, _same_cov, _raw = H._fitv, H._same(OUTPUTS), H._same_cov, functools.partial(H._raw, "dyn")
 
 
 def _matches(e, name, lam, label=""):
@@ -57,28 +37,7 @@ def _matches(e, name, lam, label=""):
     assert np.all(got["edge_leverage"] > 0.0) and np.all(got["edge_leverage"] <= 6.0)
     assert Q.rel(got["edge_omega"], r.edge_omega) <= 1e-10         # (a cost share: the bar of c0 in tests/schur_dyn_cases.py)
     assert om <= 1e-12
-    # statistics and totals: against the reference, and against the device's own rows (maxima and counts exactly)
-    w, fit = d["w"], got["fit"]
-    for key, index, size in (("lm_stats", d["landmark_of_row"], e.L), ("pose_stats", d["pose_of_row"], e.n)):
-        own = Q.stats_of(got["leverage"], got["wtest"], w, index, size)
-        assert np.abs(got[key][:, 0] - own[:, 0]).max() <= np.bincount(index).max() * EPS * np.abs(own[:, 0]).max()
-        assert np.array_equal(got[key][:, 1:], own[:, 1:])
-        ref = getattr(r, key)
-        assert Q.rel(got[key][:, 0], ref[:, 0]) <= Q.bar(r, "leverage") and Q.rel(got[key][:, 1], ref[:, 1]) <= Q.bar(r, "wtest")
-        assert np.array_equal(got[key][:, 2], ref[:, 2])
-    fin = lambda a: float(np.max(a[np.isfinite(a)], initial=0.0))
-    assert fit["m_eff"] == r.fit["m_eff"] == float((w > 0).sum()) and fit["max_wtest"] == fin(got["wtest"]) and fit["max_lm_wtest"] == fin(got["lm_wtest"])
-    ne = e.n - 1
-    for k, own, cnt in (("t_rows", got["leverage"], e.m), ("t_prior", got["lm_leverage"], e.L), ("t_edges", got["edge_leverage"], ne),
-                        ("omega_edges", got["edge_omega"], ne)):
-        assert abs(fit[k] - own.sum()) <= cnt * EPS * abs(fit[k]), k
-    assert fit["rho"] == ((((2.0 * fit["m_eff"] + 3.0 * e.L) + 6.0 * ne) - fit["t_rows"]) - fit["t_prior"]) - fit["t_edges"]
-    assert fit["s0sq"] == fit["omega"] / fit["rho"]
-    # (a trace within the bar of its family, relative to the largest entry, times the number of entries)
-    for k, fam, cnt, top in (("t_rows", "leverage", e.m, r.leverage.max()), ("t_prior", "lm_leverage", e.L, r.lm_leverage.max()),
-                             ("t_edges", "edge_leverage", ne, r.edge_leverage.max())):
-        assert abs(fit[k] - r.fit[k]) <= cnt * top * Q.bar(r, fam), k
-    assert abs(fit["rho"] - r.fit["rho"]) <= 1e-9 * r.unknowns and abs(fit["s0sq"] - r.fit["s0sq"]) <= 1e-9 * r.fit["s0sq"]
+    H.statistics_and_totals("dyn", Q, d, e, got, r)
     return got, r
 
 
@@ -101,16 +60,6 @@ def test_matches_the_reference(name, lam):
 
 
 # ------------------------------------------------------------------------------------------------ 2. failure case
-def _raw(e, lam, on=(True,) * 9):
-    """The C entry itself: (rc, info, outputs in the order of OUTPUTS, device row order); outputs not asked for are None (NULL)."""
-    from vinsat_amd._lib import PD
-    shapes = ((e.m,), (e.m,), (e.L,), (e.L,), (e.L, 3), (e.n, 3), (e.n - 1,), (e.n - 1,), (10,))
-    bufs = [np.full(s, 7.0) if o else None for s, o in zip(shapes, on)]
-    info = ctypes.c_int(-1)
-    rc = e.lib.vba_schur_reliability_dyn(e.h, float(lam), *[b.ctypes.data_as(PD) if b is not None else None for b in bufs], ctypes.byref(info))
-    return (rc, info.value, *bufs)
-
-
 def test_failed_factorisation_gives_nan_and_the_row():
     from vinsat_amd._lib import VbaError
     name, lam = Q.FAILURE

@@ -25,6 +25,7 @@ import pytest
 import schur_cases as C
 import schur_dyn_cases as DC
 import schur_power_cases as PW
+import schur_query_harness as H
 import schur_rel_cases as R
 
 pytestmark = pytest.mark.gpu
@@ -34,12 +35,8 @@ NCP, CRIT = PW.NCP, 3.29
 
 
 def _open(name=None, d=None, state=None, dyn=False):
-    from vinsat_amd.schur import SchurBA
     d = (DC.case(name) if dyn else R.problem(name)) if d is None else d
-    extra = dict(time_idx=d["time_idx"], sigma_dyn=d["sigma_dyn"]) if dyn else {}
-    e = SchurBA(d["states0"], d["X0"], d["uv"], d["w"], d["pose_of_row"], d["landmark_of_row"], d["intrinsics"], sigma_prior=d["sigma"], **extra)
-    e.set_state(*(state or (d["states0"], d["Xs"])))
-    return d, e
+    return d, H.engine(d, dynamics=dyn, state=state)
 
 
 def _ask(e, dyn, *a, **k):
@@ -54,9 +51,7 @@ def _bits(a):
     return [np.asarray(a[k]).tobytes() for k in OUTPUTS[:-1]] + [np.array(list(a["fit"].values())).tobytes(), a["info"]]
 
 
-def _fin_max(a):
-    a = np.asarray(a)
-    return float(np.max(a[np.isfinite(a)], initial=0.0))
+_fin_max = H.fin_max
 
 
 def _consistent(d, e, got, rel, crit, dyn):
@@ -146,15 +141,9 @@ def test_landmarks_without_rows_and_singular_priors():
     e.close()
 
 
-def _raw(e, lam, on=(True,) * 11, ncp=NCP, crit=CRIT, dyn=False):
+def _raw(e, lam, on=None, ncp=NCP, crit=CRIT, dyn=False):
     """The C entry itself: (rc, info, outputs in the order of OUTPUTS, device row order); outputs not asked for are None (NULL)."""
-    from vinsat_amd._lib import PD
-    shapes = ((e.m,),) * 6 + ((e.L,),) * 3 + ((e.n, 4), (14 if dyn else 12,))
-    bufs = [np.full(s, 7.0) if o else None for s, o in zip(shapes, on)]
-    info = ctypes.c_int(-1)
-    entry = e.lib.vba_schur_outlier_power_dyn if dyn else e.lib.vba_schur_outlier_power
-    rc = entry(e.h, float(lam), float(ncp), float(crit), *[b.ctypes.data_as(PD) if b is not None else None for b in bufs], ctypes.byref(info))
-    return (rc, info.value, *bufs)
+    return H.raw_query(e, "vba_schur_outlier_power_dyn" if dyn else "vba_schur_outlier_power", lam, on, ncp=ncp, crit=crit)
 
 
 @pytest.mark.parametrize("dyn", [False, True])

@@ -11,46 +11,30 @@ Every test here needs the entry point and fails where it does not exist.
 Device against reference, measured on an MI355X: see DESIGN section 9.2.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import schur_cases as C
+import schur_query_harness as H
 import schur_rel_cases as R
 
 pytestmark = pytest.mark.gpu
-EPS = np.finfo(np.float64).eps
-OUTPUTS = ("leverage", "wtest", "lm_leverage", "lm_wtest", "lm_stats", "pose_stats", "fit")
+OUTPUTS = H.REL_OUTPUTS["plain"]
+_same, _raw = H._same(OUTPUTS), functools.partial(H._raw, "plain")
 
 
 def _open(name=None, d=None, state=None):
-    from vinsat_amd.schur import SchurBA
     d = R.problem(name) if d is None else d
-    e = SchurBA(d["states0"], d["X0"], d["uv"], d["w"], d["pose_of_row"], d["landmark_of_row"], d["intrinsics"], sigma_prior=d["sigma"])
-    e.set_state(*(state or (d["states0"], d["Xs"])))
-    return d, e
-
-
-def _same(a, b):
-    """Bitwise equal dicts of ``SchurBA.reliability`` (NaN equal to NaN)."""
-    return all(np.array_equal(a[k], b[k], equal_nan=True) for k in OUTPUTS[:-1]) and \
-        np.array_equal(np.array(list(a["fit"].values())), np.array(list(b["fit"].values())), equal_nan=True) and a["info"] == b["info"]
+    return d, H.engine(d, state=state)
 
 
 def _consistent(d, e, got, lam):
     """Statistics and totals against the device's own rows (sums to rounding of another order, maxima and counts exactly), and the
     trace identity ``t_rows + t_prior + lamda tr(H^-1) = 6 n + 3 L`` with the trace from the device's covariance blocks."""
-    w, fit = d["w"], got["fit"]
-    for key, index, size in (("lm_stats", d["landmark_of_row"], e.L), ("pose_stats", d["pose_of_row"], e.n)):
-        ref = R.stats_of(got["leverage"], got["wtest"], w, index, size)
-        # (a sum of t non-negative terms in another order: within t eps of it)
-        assert np.abs(got[key][:, 0] - ref[:, 0]).max() <= np.bincount(index).max() * EPS * np.abs(ref[:, 0]).max()
-        assert np.array_equal(got[key][:, 1:], ref[:, 1:])
-    fin = lambda a: float(np.max(a[np.isfinite(a)], initial=0.0))
-    assert fit["m_eff"] == float((w > 0).sum()) and fit["max_wtest"] == fin(got["wtest"]) and fit["max_lm_wtest"] == fin(got["lm_wtest"])
-    assert abs(fit["t_rows"] - got["leverage"].sum()) <= e.m * EPS * fit["t_rows"] and abs(fit["t_prior"] - got["lm_leverage"].sum()) <= e.L * EPS * fit["t_prior"]
-    assert fit["rho"] == ((2.0 * fit["m_eff"] + 3.0 * e.L) - fit["t_rows"]) - fit["t_prior"]
-    assert fit["s0sq"] == fit["omega"] / fit["rho"]
+    fit = got["fit"]
+    H.statistics_and_totals("plain", R, d, e, got)
     c = e.covariance(lam)
     trace = np.trace(c["pose"], axis1=1, axis2=2).sum() + np.trace(c["landmark"], axis1=1, axis2=2).sum()
     ident = fit["t_rows"] + fit["t_prior"] + lam * trace
@@ -170,16 +154,6 @@ def test_displaced_catalogue_entry_ranks_first():
     rows, lms = suspects(got, crit)
     assert rows.size == 0 and np.array_equal(lms, [d["displaced_lm"]])
     e.close()
-
-
-def _raw(e, lam, on=(True,) * 7):
-    """The C entry itself: (rc, info, outputs in the order of OUTPUTS, device row order); outputs not asked for are None (NULL)."""
-    from vinsat_amd._lib import PD
-    shapes = ((e.m,), (e.m,), (e.L,), (e.L,), (e.L, 3), (e.n, 3), (8,))
-    bufs = [np.full(s, 7.0) if o else None for s, o in zip(shapes, on)]
-    info = ctypes.c_int(-1)
-    rc = e.lib.vba_schur_reliability(e.h, float(lam), *[b.ctypes.data_as(PD) if b is not None else None for b in bufs], ctypes.byref(info))
-    return (rc, info.value, *bufs)
 
 
 @pytest.mark.parametrize("mode", ["0", "1", "2"])

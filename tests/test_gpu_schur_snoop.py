@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import schur_cases as C
+import schur_query_harness as H
 import schur_rel_cases as R
 import schur_snoop_cases as SC
 import schur_snoop_oracle as SO
@@ -24,12 +25,8 @@ CASES = (("12", 0.0), ("12", 1e-3), ("43", 1e-3), ("pose_without_rows", 1e-3), (
 
 
 def _open(name=None, d=None, state=None, w=None):
-    from vinsat_amd.schur import SchurBA
     d = R.problem(name) if d is None else d
-    e = SchurBA(d["states0"], d["X0"], d["uv"], d["w"] if w is None else w, d["pose_of_row"], d["landmark_of_row"], d["intrinsics"],
-                sigma_prior=d["sigma"])
-    e.set_state(*(state or (d["states0"], d["Xs"])))
-    return d, e
+    return d, H.engine(d, state=state, w=w)
 
 
 def _shaken(d):
@@ -42,9 +39,7 @@ def _shaken(d):
     return d["states0"], X
 
 
-def _same_rel(a, b):
-    return all(np.array_equal(a[k], b[k], equal_nan=True) for k in REL_OUTPUTS) and a["info"] == b["info"] and \
-        np.array_equal(np.array(list(a["fit"].values())), np.array(list(b["fit"].values())), equal_nan=True)
+_same_rel = H._same(REL_OUTPUTS)
 
 
 def _same_cov(a, b):

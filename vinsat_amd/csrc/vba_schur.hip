@@ -15,17 +15,23 @@
 // d uv / d X = A R^T = -(translation part of the pose Jacobian).  Weights are the observation confidences (the
 // reference's alpha = 2 case, BA_filtering.py:22-25, where the robust weight is constant) until vba_schur_reweight is called.
 //
-// Units (vba_schur_context.h is what they share: the view, the handle, error reporting, the scratch of a feature):
-//   vba_schur.hip         this file: the handle's lifecycle, one LM trial (vba_schur_iterate), substitutions, update, cost
+// Units (vba_schur_context.h is what they share: the view, the handle, error reporting, the scratch of a feature, the scaffold of
+// the query entries):
+//   vba_schur.hip         this file: the handle's lifecycle, one LM trial (vba_schur_iterate), substitutions, update, cost; the scaffold
+//                         of the eleven query entries (schur_kind_check: which kind of handle an entry serves; schur_query_begin: what
+//                         runs before a device part; schur_outputs_finish: NaN or the copies to the host; schur_last_ms in the header)
 //   vba_schur_build.hip   k_lm_blocks, k_pose_blocks, k_pair_blocks, k_pad_identity
 //   vba_schur_factor.hip  k_potrf64, k_potrf64b, k_gemm_abt, k_syrk_panel and the order of their launches
-//   vba_schur_cov.hip     vba_schur_covariance: k_trinv_step, k_syrk_wtw, k_cov_gather, k_lm_cov; vba_schur_covariance_dyn on top:
-//                         k_syrk_wtw_sel, k_state_gather (index map and tile list: vba_schur_dyn_cov.h)
-//   vba_schur_rel.hip     vba_schur_reliability: k_rel_rows, k_rel_stats, k_rel_totals; vba_schur_reliability_dyn on top:
-//                         k_rel_edges, k_rel_edge_totals (closed form of the edge leverage: vba_schur_dyn_rel.h)
-//   vba_schur_power.hip   vba_schur_outlier_power, vba_schur_outlier_power_dyn: k_pow_rows (in the place of k_rel_rows: one gather per
+//   vba_schur_cov.hip     vba_schur_covariance, vba_schur_covariance_dyn behind one device part (schur_query_device, the handle decides):
+//                         k_trinv_step, k_syrk_wtw, k_cov_gather, k_lm_cov; with the dynamics factor k_syrk_wtw_sel, k_state_gather (index
+//                         map and tile list: vba_schur_dyn_cov.h)
+//   vba_schur_rel.hip     vba_schur_reliability, _dyn, _att behind one body and one device part (schur_rel_call, schur_rel_device, folded
+//                         over the kind of handle): k_rel_rows, k_rel_stats, k_rel_totals; with the dynamics factor k_rel_edges,
+//                         k_rel_edge_totals (vba_schur_dyn_rel.h); with the attitude factor k_rel_att_edges, k_rel_att_totals
+//                         (vba_schur_att_rel.h)
+//   vba_schur_power.hip   vba_schur_outlier_power, _dyn, _att behind schur_power_call: k_pow_rows (in the place of k_rel_rows: one gather per
 //                         row, vba_schur_rowpass.h), k_pow_stats, k_pow_totals (closed forms: vba_power_math.h, vba_schur_power_math.h)
-//   vba_schur_snoop.hip   vba_schur_snoop, vba_schur_snoop_dyn, vba_schur_rejected, vba_schur_snoop_restore and their passes
+//   vba_schur_snoop.hip   vba_schur_snoop, _dyn, _att behind schur_snoop_call, vba_schur_rejected, vba_schur_snoop_restore and their passes
 //   vba_schur_robust.hip  vba_schur_reweight, vba_schur_get_weights, vba_schur_median and their passes
 //   vba_schur_dyn.hip     vba_schur_enable_dynamics and the kernels of the factor
 //   vba_schur_att.hip     vba_schur_enable_attitude and the kernels of the Gauss-Newton attitude factor (bodies: vba_schur_att_math.h)
@@ -55,14 +61,17 @@
 // k_rel_rows and k_rel_stats as above, then)
 //   k_rel_edges        eight lanes per dynamics edge, six at work: a diagonal entry of J Sigma12 J^T each, the edge's leverage
 //   k_rel_edge_totals  one block behind k_rel_totals: the edges' leverages and cost shares folded into the fit
-// Outlier power (vba_schur_outlier_power, vba_schur_outlier_power_dyn: the device part of the reliability query of the handle with
-// k_pow_rows as its row pass, then)
+// Reliability of a handle with the attitude factor too (vba_schur_reliability_att: the launches above in their order, then)
+//   k_rel_att_edges    thread per attitude edge: P_a from the attitude components of the 9x9 blocks, its leverage and w-test
+//   k_rel_att_totals   one block behind k_rel_edge_totals: the attitude edges' leverages, cost shares and largest test folded into the fit
+// Outlier power (vba_schur_outlier_power, _dyn, _att: the device part of the reliability query of the handle's kind with k_pow_rows
+// as its row pass, then)
 //   k_pow_rows      thread per row: the gather and P_k of k_rel_rows (lev, wt, om with its bits), then B_k = w Sigma_k J_k^T, detectable
 //                   bias, external reliability in position, attitude and landmark, the row's influence, the pull of the prior
 //   k_pow_stats     thread per landmark: detectable catalogue error, its effect on the landmark, the worst-hit pose; per pose: pose_fit
 //   k_pow_totals    one block: the fit of the reliability query and four slots behind it (the tree of k_rel_totals)
-// Data snooping (vba_schur_snoop: the device part of the reliability query, then the passes of vba_schur_snoop.hip;
-// vba_schur_snoop_dyn: the same passes behind the device part of vba_schur_reliability_dyn)
+// Data snooping (vba_schur_snoop, _dyn, _att: the device part of the reliability query of the handle's kind, then the passes of
+// vba_schur_snoop.hip)
 // Robust re-weighting (vba_schur_reweight, vba_schur_median: the passes of vba_schur_robust.hip)
 // Orbit-dynamics factor with velocity unknowns (vba_schur_enable_dynamics: the kernels of vba_schur_dyn.hip; the reduced system
 // becomes [6 n pose | 3 n velocity] unknowns, the build and factor kernels fill and factorise it unchanged)
@@ -206,6 +215,38 @@ void schur_scratch_release(SchurScratch& Z) {
     for (hipEvent_t e : Z.ev) if (e) hipEventDestroy(e);
     if (Z.arena) hipFree(Z.arena);
     Z = SchurScratch{};
+}
+
+// ------------------------------------------------------------------------------------------------ scaffold of the query entries
+int schur_kind_check(SchurKind kind, vba_schur_handle h, const char* entry) {
+    if (kind == kSchurPlain) return h->dyn.enabled ? sfail(VBA_ESTATE, std::string(entry) + kDynRefusal) : VBA_OK;
+    if (!h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
+    if (kind == kSchurAtt && !h->att.enabled) return sfail(VBA_ESTATE, "the attitude factor is not enabled on this handle");
+    if (kind == kSchurDyn && h->att.enabled && entry) return sfail(VBA_ESTATE, std::string(entry) + kAttRefusal);
+    return VBA_OK;
+}
+
+int schur_query_begin(vba_schur_handle h, SchurKind kind, const char* entry) {
+    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
+    if (int rc = schur_kind_check(kind, h, entry)) return rc;
+    SCHK(hipSetDevice(h->device));
+    if (int rc = schur_query_alloc(h)) return rc;
+    return schur_query_index(h);
+}
+
+int schur_outputs_finish(SchurScratch& Z, hipStream_t s, int bad, const Out* outs, size_t count) {
+    if (bad != 0) {
+        if (int rc = schur_scratch_finish(Z, s)) return rc;
+        for (size_t k = 0; k < count; ++k)
+            if (outs[k].host) std::fill(outs[k].host, outs[k].host + outs[k].count, std::nan(""));
+        return VBA_OK;
+    }
+    return schur_scratch_finish(Z, s, [&]() -> int {
+        SCHK(hipGetLastError());
+        for (size_t k = 0; k < count; ++k)
+            if (outs[k].host) SCHK(hipMemcpyAsync(outs[k].host, outs[k].dev, outs[k].count * 8, hipMemcpyDeviceToHost, s));
+        return VBA_OK;
+    });
 }
 
 static int schur_cost(vba_schur_handle h, const double* states, const double* X, double* cost) {

@@ -1,7 +1,8 @@
 // vba_schur_context.h -- the host side of the free-landmark mode shared by its translation units (the map of the units and of
 // their kernels heads vba_schur.hip): the view the kernels take, the row geometry three units reproject with, the context behind a
-// vba_schur_handle with the state of every feature, error reporting, the scratch helper behind the features, and the functions one
-// unit defines and another calls.  Internal.
+// vba_schur_handle with the state of every feature, error reporting, the scratch helper behind the features, the scaffold of the
+// query entries (which kind of handle an entry serves, what runs before its device part, how its outputs reach the host), and the
+// functions one unit defines and another calls.  Internal.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -239,11 +240,11 @@ struct SchurAtt {
 constexpr char kAttRefusal[] = " is not available on a handle with the attitude factor: its redundancy counts and edge leverages do not "
                                "know the 3 (n - 1) attitude equations";
 
-// why the three queries refuse a handle with the dynamics factor (vba_schur_covariance_dyn is the covariance query of such a handle)
+// why the plain-named queries refuse a handle with the dynamics factor (vba_schur_covariance_dyn is the covariance query of such a handle)
 constexpr char kDynRefusal[] = " is not available on a handle with the dynamics factor: its redundancy counts and gathers assume the "
                                "6 n reduced system of the reprojection rows";
 
-// which handle a body shared by three entries serves: the plain one, one with the dynamics factor, one with the attitude factor too
+// which handle an entry serves: the plain one, one with the dynamics factor, one with the attitude factor too
 enum SchurKind { kSchurPlain = 0, kSchurDyn = 1, kSchurAtt = 2 };
 
 struct vba_schur_context {
@@ -291,24 +292,39 @@ int schur_factor_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, i
 int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn = nullptr,
                        const SchurAttView* att = nullptr);
 
+// -- the scaffold of the query entries (covariance, reliability, snoop, outlier power)
+// VBA_OK, or why an entry of this kind does not serve this handle: the one place that decides it.  `entry` goes in front of the
+// refusal: the entry's own name for a plain-named entry (kDynRefusal), the name of the dynamics-only counterpart for a _dyn or an
+// _att entry (kAttRefusal); nullptr: a _dyn entry that serves a handle with the attitude factor too (vba_schur_covariance_dyn).
+// A plain-named entry asks before it looks at its arguments, the others behind them (schur_query_begin asks for every entry).
+int schur_kind_check(SchurKind kind, vba_schur_handle h, const char* entry);
+// What every query entry does between its argument checks and the allocations of its own feature: problem and state are there,
+// the kind of the handle is the entry's, the device is current, the query scratch and its index exist.
+int schur_query_begin(vba_schur_handle h, SchurKind kind, const char* entry);
+// One output of a query: where the caller wants it (nullptr: not asked for), where it lies on the device, how many doubles.
+struct Out { double* host; const double* dev; size_t count; };
+// End of a query whose timed section began at Z.ev[0] (schur_scratch_finish).  bad != 0 (no factor, no covariance, no figure): NaN
+// into every output asked for.  Else the copies to the host behind ev[1]: what is asked for decides the copies only.
+int schur_outputs_finish(SchurScratch& Z, hipStream_t s, int bad, const Out* outs, size_t count);
+// the body of a vba_schur_last_*_ms getter: the last reading of the scratch of one feature (&vba_schur_context::q, ::rel, ...)
+template <class Feature>
+int schur_last_ms(vba_schur_handle h, Feature vba_schur_context::*feature, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = (h->*feature).sc.ms;
+    return VBA_OK;
+}
+
 // ---- vba_schur_cov.hip
 int schur_query_alloc(vba_schur_handle h);
 int schur_query_index(vba_schur_handle h);
+// the device part of the covariance query of the handle, plain or with the dynamics factor (h->dyn.enabled decides)
 int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad);
-int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad);
 
 // ---- vba_schur_rel.hip
 int schur_rel_alloc(vba_schur_handle h);
-int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
-int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
-int schur_rel_device_att(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
-// the device part of the reliability query of a handle of this kind
-inline int schur_rel_device_of(SchurKind kind, vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0) {
-    return kind == kSchurAtt ? schur_rel_device_att(h, lamda, ev_begin, V, bad, pow_ncp)
-         : kind == kSchurDyn ? schur_rel_device_dyn(h, lamda, ev_begin, V, bad, pow_ncp) : schur_rel_device(h, lamda, ev_begin, V, bad, pow_ncp);
-}
-// VBA_OK, or why an entry of this kind (`dyn_entry`: the name of its dynamics-only counterpart) does not serve this handle
-int schur_kind_check(SchurKind kind, vba_schur_handle h, const char* dyn_entry);
+// the device part of the reliability query of a handle of this kind (checked by the caller); pow_ncp > 0: the row pass of the
+// outlier power query in the place of k_rel_rows
+int schur_rel_device(vba_schur_handle h, SchurKind kind, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp = 0.0);
 
 // ---- vba_schur_power.hip
 // k_pow_rows on the handle's stream in the place of k_rel_rows (the power scratch is allocated): lev, wt, om of the reliability

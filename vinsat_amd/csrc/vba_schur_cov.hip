@@ -1,7 +1,7 @@
-// vba_schur_cov.hip -- the covariance query of the free-landmark mode (vba_schur_covariance; include/vinsat_ba.h carries the
-// contract): build and factor into scratch of its own, then the selected blocks of the inverse.  Its device part is what
-// vba_schur_reliability and vba_schur_snoop start with.  vba_schur_covariance_dyn, the query of a handle with the dynamics factor,
-// follows it: the same stages over [6 n pose | 3 n velocity] unknowns.  vba_schur.hip carries the map of the units.
+// vba_schur_cov.hip -- the covariance query of the free-landmark mode (vba_schur_covariance, and vba_schur_covariance_dyn on a handle
+// with the dynamics factor: the same stages over [6 n pose | 3 n velocity] unknowns; include/vinsat_ba.h carries the contracts): build
+// and factor into scratch of its own, then the selected blocks of the inverse.  One device part serves both (schur_query_device); it is
+// what the reliability, snoop and outlier power queries start with.  vba_schur.hip carries the map of the units.
 #include "vba_schur_context.h"
 #include "vba_schur_dyn_cov.h"
 
@@ -293,16 +293,30 @@ static SchurView query_view(vba_schur_handle h, double lamda) {
     return V;
 }
 
-// The device part of vba_schur_covariance, shared with vba_schur_reliability: ev_begin, then build and factorise into the query's
-// scratch at this damping (V: the view that was built -- the handle's problem, everything written in the scratch), the info word
-// to the host (*bad), and unless the factorisation failed the selected inverse, the gathered blocks (Q.pair, Q.pose) and, with
-// with_lm, the landmark marginals (Q.lm).  The launches and their order are those vba_schur_covariance has always issued.
+// The device part of the covariance query, shared with the reliability query (vba_schur_rel.hip): ev_begin, then build and factorise
+// into the query's scratch at this damping (V: the view that was built -- the handle's problem, everything written in the scratch),
+// the info word to the host (*bad), and unless the factorisation failed the selected inverse, the gathered blocks (Q.pair, Q.pose)
+// and, with with_lm, the landmark marginals (Q.lm).  On a handle with the dynamics factor (the entries check the kind first, so the
+// handle decides): the dynamics blocks of the build go through arrays of the scratch (DW; TW likewise on a handle with the attitude
+// factor, so debug_fetch 7 .. 9 stay the last iterate's), W is needed in full (h->bw = nb - 1: nothing skipped), the product forms the
+// listed tiles of S9^-1 only (every tile with VBA_SCHUR_COV_FULL=1), the 9x9 blocks are gathered (Q.state, Q.edge), and k_cov_gather /
+// k_lm_cov run as they are: they index by V.Npad and read the top-left 6 n x 6 n only (E9 has no velocity rows, so the landmark
+// formula stands).  The reliability query reads what this leaves resident: Q.state, Q.edge, Q.pair, Q.lm, Q.dyn_A, Q.dyn_ecost.  The
+// launches and their order are those the two queries have always issued.
 int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad) {
     SchurQuery& Q = h->q;
     hipStream_t s = h->stream;
+    const bool dyn = h->dyn.enabled, att = dyn && h->att.enabled;
     V = query_view(h, lamda);
+    SchurDynView DW{};
+    SchurAttView TW{};
+    if (dyn) {
+        DW = schur_dyn_view(h, V);
+        DW.r = Q.dyn_r; DW.A = Q.dyn_A; DW.ecost = Q.dyn_ecost; DW.part = Q.dyn_part;
+    }
+    if (att) TW = schur_att_view(h, V, true);
     SCHK(hipEventRecord(ev_begin, s));
-    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr)) return rc;
+    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr, dyn ? &DW : nullptr, att ? &TW : nullptr)) return rc;
     SCHK(hipGetLastError());
     *bad = 0;
     SCHK(hipMemcpyAsync(bad, Q.info, 4, hipMemcpyDeviceToHost, s));
@@ -311,41 +325,30 @@ int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_
     const int nbu = (V.N + kT - 1) / kT;
     const size_t n_pair = (size_t)V.nblk * 36;
     for (int d = 0; d < nbu; ++d) hipLaunchKernelGGL(k_trinv_step, dim3(nbu - d), dim3(256), 0, s, V, Q.W, d, h->bw);
-    hipLaunchKernelGGL(k_syrk_wtw, dim3(nbu * (nbu + 1) / 2), dim3(256), 0, s, V, Q.W, Q.S, nbu);      // (over the factor: no longer needed)
+    // (over the factor: no longer needed)
+    if (!dyn || h->cov_full) hipLaunchKernelGGL(k_syrk_wtw, dim3(nbu * (nbu + 1) / 2), dim3(256), 0, s, V, Q.W, Q.S, nbu);
+    else hipLaunchKernelGGL(k_syrk_wtw_sel, dim3(Q.ntiles), dim3(256), 0, s, V, Q.W, Q.S, nbu, Q.tiles);
+    if (dyn) hipLaunchKernelGGL(k_state_gather, dim3((81 * (2 * V.n - 1) + 255) / 256), dim3(256), 0, s, V, Q.S, Q.state, Q.edge);
     hipLaunchKernelGGL(k_cov_gather, dim3((unsigned)((n_pair + 255) / 256)), dim3(256), 0, s, V, Q.S, Q.pair, Q.pose);
     if (with_lm) hipLaunchKernelGGL(k_lm_cov, dim3((V.L + 255) / 256), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm);
     return VBA_OK;
 }
 
-// The device part of vba_schur_covariance_dyn, as schur_query_device but on a handle with the dynamics factor: the dynamics blocks
-// of the build go through arrays of the scratch (DW), W is needed in full (h->bw = nb - 1: nothing skipped), then the listed tiles
-// of S9^-1 (every tile with VBA_SCHUR_COV_FULL=1), the 9x9 blocks, and k_cov_gather / k_lm_cov as they are: they index by V.Npad
-// and read the top-left 6 n x 6 n only (E9 has no velocity rows, so the landmark formula stands).  Shared with
-// vba_schur_reliability_dyn (vba_schur_rel.hip), which reads what it leaves resident: Q.state, Q.edge, Q.pair, Q.lm, Q.dyn_A, Q.dyn_ecost.
-int schur_query_device_dyn(vba_schur_handle h, double lamda, bool with_lm, hipEvent_t ev_begin, SchurView& V, int* bad) {
+// Behind the checks of the two entries: the scaffold, the device part from the query's own ev[0], *info, and the outputs -- the
+// leading blocks are [n] 6x6 pose blocks or [n] 9x9 state and [n - 1] 9x9 edge blocks, pair_cov and lm_cov follow for both.
+static int schur_cov_call(vba_schur_handle h, SchurKind kind, double lamda, double* lead_cov, double* edge_cov, double* pair_cov, double* lm_cov,
+                          int* info) {
+    if (int rc = schur_query_begin(h, kind, kind == kSchurPlain ? "vba_schur_covariance" : nullptr)) return rc;
     SchurQuery& Q = h->q;
-    hipStream_t s = h->stream;
-    V = query_view(h, lamda);
-    SchurDynView DW = schur_dyn_view(h, V);
-    DW.r = Q.dyn_r; DW.A = Q.dyn_A; DW.ecost = Q.dyn_ecost; DW.part = Q.dyn_part;
-    // (a handle with the attitude factor: the arrays that factor keeps for this build, so debug_fetch 7 .. 9 stay the last iterate's)
-    const SchurAttView TW = h->att.enabled ? schur_att_view(h, V, true) : SchurAttView{};
-    SCHK(hipEventRecord(ev_begin, s));
-    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr, &DW, h->att.enabled ? &TW : nullptr)) return rc;
-    SCHK(hipGetLastError());
-    *bad = 0;
-    SCHK(hipMemcpyAsync(bad, Q.info, 4, hipMemcpyDeviceToHost, s));
-    SCHK(hipStreamSynchronize(s));
-    if (*bad != 0) return VBA_OK;
-    const int nbu = (V.N + kT - 1) / kT;
-    const size_t n_pair = (size_t)V.nblk * 36;
-    for (int d = 0; d < nbu; ++d) hipLaunchKernelGGL(k_trinv_step, dim3(nbu - d), dim3(256), 0, s, V, Q.W, d, h->bw);
-    if (h->cov_full) hipLaunchKernelGGL(k_syrk_wtw, dim3(nbu * (nbu + 1) / 2), dim3(256), 0, s, V, Q.W, Q.S, nbu);
-    else hipLaunchKernelGGL(k_syrk_wtw_sel, dim3(Q.ntiles), dim3(256), 0, s, V, Q.W, Q.S, nbu, Q.tiles);
-    hipLaunchKernelGGL(k_state_gather, dim3((81 * (2 * V.n - 1) + 255) / 256), dim3(256), 0, s, V, Q.S, Q.state, Q.edge);
-    hipLaunchKernelGGL(k_cov_gather, dim3((unsigned)((n_pair + 255) / 256)), dim3(256), 0, s, V, Q.S, Q.pair, Q.pose);
-    if (with_lm) hipLaunchKernelGGL(k_lm_cov, dim3((V.L + 255) / 256), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm);
-    return VBA_OK;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_query_device(h, lamda, lm_cov != nullptr, Q.sc.ev[0], V, &bad)) return rc;
+    *info = bad;
+    const size_t n = (size_t)V.n;
+    const bool dyn = kind != kSchurPlain;
+    const Out outs[4] = {{lead_cov, dyn ? Q.state : Q.pose, dyn ? n * 81 : n * 36}, {edge_cov, Q.edge, dyn ? (n - 1) * 81 : 0},
+                         {pair_cov, Q.pair, (size_t)V.nblk * 36}, {lm_cov, Q.lm, (size_t)V.L * 9}};
+    return schur_outputs_finish(Q.sc, h->stream, bad, outs, 4);
 }
 
 extern "C" {
@@ -353,77 +356,18 @@ extern "C" {
 int vba_schur_covariance_dyn(vba_schur_handle h, double lamda, double* state_cov, double* edge_cov, double* pair_cov, double* lm_cov, int* info) {
     if (!h || !info || !state_cov || !edge_cov) return sfail(VBA_EINVAL, "null argument");
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
-    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    if (!h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
-    SCHK(hipSetDevice(h->device));
-    if (int rc = schur_query_alloc(h)) return rc;
-    if (int rc = schur_query_index(h)) return rc;
-    SchurQuery& Q = h->q;
-    hipStream_t s = h->stream;
-    SchurView V;
-    int bad = 0;
-    if (int rc = schur_query_device_dyn(h, lamda, lm_cov != nullptr, Q.sc.ev[0], V, &bad)) return rc;
-    *info = bad;
-    const size_t n_state = (size_t)V.n * 81, n_edge = (size_t)(V.n - 1) * 81, n_pair = (size_t)V.nblk * 36, n_lm = (size_t)V.L * 9;
-    if (bad != 0) {                 // no factor, no covariance: NaN, and the row in *info
-        if (int rc = schur_scratch_finish(Q.sc, s)) return rc;
-        std::fill(state_cov, state_cov + n_state, std::nan(""));
-        std::fill(edge_cov, edge_cov + n_edge, std::nan(""));
-        if (pair_cov) std::fill(pair_cov, pair_cov + n_pair, std::nan(""));
-        if (lm_cov) std::fill(lm_cov, lm_cov + n_lm, std::nan(""));
-        return VBA_OK;
-    }
-    return schur_scratch_finish(Q.sc, s, [&]() -> int {
-        SCHK(hipGetLastError());
-        SCHK(hipMemcpyAsync(state_cov, Q.state, n_state * 8, hipMemcpyDeviceToHost, s));
-        SCHK(hipMemcpyAsync(edge_cov, Q.edge, n_edge * 8, hipMemcpyDeviceToHost, s));
-        if (pair_cov) SCHK(hipMemcpyAsync(pair_cov, Q.pair, n_pair * 8, hipMemcpyDeviceToHost, s));
-        if (lm_cov) SCHK(hipMemcpyAsync(lm_cov, Q.lm, n_lm * 8, hipMemcpyDeviceToHost, s));
-        return VBA_OK;
-    });
+    return schur_cov_call(h, kSchurDyn, lamda, state_cov, edge_cov, pair_cov, lm_cov, info);
 }
 
-int vba_schur_last_covariance_dyn_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->q.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_covariance_dyn_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::q, ms); }
 
 int vba_schur_covariance(vba_schur_handle h, double lamda, double* pose_cov, double* pair_cov, double* lm_cov, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_covariance") + kDynRefusal);
+    if (int rc = schur_kind_check(kSchurPlain, h, "vba_schur_covariance")) return rc;
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
-    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    SCHK(hipSetDevice(h->device));
-    if (int rc = schur_query_alloc(h)) return rc;
-    if (int rc = schur_query_index(h)) return rc;
-    SchurQuery& Q = h->q;
-    hipStream_t s = h->stream;
-    SchurView V;
-    int bad = 0;
-    if (int rc = schur_query_device(h, lamda, lm_cov != nullptr, Q.sc.ev[0], V, &bad)) return rc;
-    *info = bad;
-    const size_t n_pose = (size_t)V.n * 36, n_pair = (size_t)V.nblk * 36, n_lm = (size_t)V.L * 9;
-    if (bad != 0) {                 // no factor, no covariance: NaN, and the row in *info
-        if (int rc = schur_scratch_finish(Q.sc, s)) return rc;
-        if (pose_cov) std::fill(pose_cov, pose_cov + n_pose, std::nan(""));
-        if (pair_cov) std::fill(pair_cov, pair_cov + n_pair, std::nan(""));
-        if (lm_cov) std::fill(lm_cov, lm_cov + n_lm, std::nan(""));
-        return VBA_OK;
-    }
-    return schur_scratch_finish(Q.sc, s, [&]() -> int {
-        SCHK(hipGetLastError());
-        if (pose_cov) SCHK(hipMemcpyAsync(pose_cov, Q.pose, n_pose * 8, hipMemcpyDeviceToHost, s));
-        if (pair_cov) SCHK(hipMemcpyAsync(pair_cov, Q.pair, n_pair * 8, hipMemcpyDeviceToHost, s));
-        if (lm_cov) SCHK(hipMemcpyAsync(lm_cov, Q.lm, n_lm * 8, hipMemcpyDeviceToHost, s));
-        return VBA_OK;
-    });
+    return schur_cov_call(h, kSchurPlain, lamda, pose_cov, nullptr, pair_cov, lm_cov, info);
 }
 
-int vba_schur_last_covariance_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->q.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_covariance_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::q, ms); }
 
 }  // extern "C"

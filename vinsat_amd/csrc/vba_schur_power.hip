@@ -180,11 +180,7 @@ int schur_power_call(vba_schur_handle h, SchurKind kind, double lamda, double nc
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!(ncp > 0.0 && ncp <= 1.79e308)) return sfail(VBA_EINVAL, "ncp must be positive and finite");
     if (!(crit > 0.0)) return sfail(VBA_EINVAL, "crit must be > 0 (+inf counts nothing)");
-    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    if (int rc = schur_kind_check(kind, h, "vba_schur_outlier_power_dyn")) return rc;
-    SCHK(hipSetDevice(h->device));
-    if (int rc = schur_query_alloc(h)) return rc;
-    if (int rc = schur_query_index(h)) return rc;
+    if (int rc = schur_query_begin(h, kind, kind == kSchurPlain ? "vba_schur_outlier_power" : "vba_schur_outlier_power_dyn")) return rc;
     if (int rc = schur_rel_alloc(h)) return rc;
     if (int rc = schur_pow_alloc(h)) return rc;
     SchurRel& R = h->rel;
@@ -192,28 +188,20 @@ int schur_power_call(vba_schur_handle h, SchurKind kind, double lamda, double nc
     hipStream_t s = h->stream;
     SchurView V;
     int bad = 0;
-    if (int rc = schur_rel_device_of(kind, h, lamda, P.sc.ev[0], V, &bad, ncp)) return rc;
+    if (int rc = schur_rel_device(h, kind, lamda, P.sc.ev[0], V, &bad, ncp)) return rc;
     *info = bad;
     const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
     const int lead = kind == kSchurAtt ? 13 : kind == kSchurDyn ? 10 : 8;
-    struct Out { double* host; const double* dev; size_t count; };
     const Out outs[11] = {{mdb, P.mdb, m}, {ext_pos, P.epos, m}, {ext_att, P.eatt, m}, {ext_lm, P.elm, m}, {del_pos, P.dpos, m}, {del_lm, P.dlm, m},
                           {lm_mdb, P.lm_mdb, L}, {lm_ext, P.lm_ext, L}, {lm_del_pos, P.lm_del, L}, {pose_fit, P.pose_fit, 4 * n},
                           {fit, P.fit, (size_t)lead + 4}};
-    if (bad != 0) {                 // no factor, no covariance, no figure: NaN, and the row in *info
-        if (int rc = schur_scratch_finish(P.sc, s)) return rc;
-        for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
-        return VBA_OK;
+    if (bad == 0) {                 // (else no factor, no covariance, no figure: NaN, and the row in *info)
+        // every output is formed whatever is asked for: what is asked for decides the copies only
+        hipLaunchKernelGGL(k_pow_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, h->q.lm, R.lev, R.wt, R.om, P.epos, P.pull, ncp, crit,
+                           P.lm_mdb, P.lm_ext, P.lm_del, P.pose_fit);
+        hipLaunchKernelGGL(k_pow_totals, dim3(1), dim3(256), 0, s, V, R.wt, P.epos, R.lmwt, P.lm_del, R.fit, lead, crit, P.fit);
     }
-    // every output is formed whatever is asked for: what is asked for decides the copies only
-    hipLaunchKernelGGL(k_pow_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, h->q.lm, R.lev, R.wt, R.om, P.epos, P.pull, ncp, crit,
-                       P.lm_mdb, P.lm_ext, P.lm_del, P.pose_fit);
-    hipLaunchKernelGGL(k_pow_totals, dim3(1), dim3(256), 0, s, V, R.wt, P.epos, R.lmwt, P.lm_del, R.fit, lead, crit, P.fit);
-    return schur_scratch_finish(P.sc, s, [&]() -> int {
-        SCHK(hipGetLastError());
-        for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
-        return VBA_OK;
-    });
+    return schur_outputs_finish(P.sc, s, bad, outs, 11);
 }
 
 }  // namespace
@@ -232,15 +220,11 @@ int vba_schur_outlier_power(vba_schur_handle h, double lamda, double ncp, double
                             double* del_pos, double* del_lm, double* lm_mdb, double* lm_ext, double* lm_del_pos, double* pose_fit, double* fit,
                             int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_outlier_power") + kDynRefusal);
+    if (int rc = schur_kind_check(kSchurPlain, h, "vba_schur_outlier_power")) return rc;
     return schur_power_call(h, kSchurPlain, lamda, ncp, crit, mdb, ext_pos, ext_att, ext_lm, del_pos, del_lm, lm_mdb, lm_ext, lm_del_pos, pose_fit, fit, info);
 }
 
-int vba_schur_last_outlier_power_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->pow.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_outlier_power_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::pow, ms); }
 
 int vba_schur_outlier_power_dyn(vba_schur_handle h, double lamda, double ncp, double crit, double* mdb, double* ext_pos, double* ext_att,
                                 double* ext_lm, double* del_pos, double* del_lm, double* lm_mdb, double* lm_ext, double* lm_del_pos, double* pose_fit,
@@ -249,11 +233,7 @@ int vba_schur_outlier_power_dyn(vba_schur_handle h, double lamda, double ncp, do
     return schur_power_call(h, kSchurDyn, lamda, ncp, crit, mdb, ext_pos, ext_att, ext_lm, del_pos, del_lm, lm_mdb, lm_ext, lm_del_pos, pose_fit, fit, info);
 }
 
-int vba_schur_last_outlier_power_dyn_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->pow.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_outlier_power_dyn_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::pow, ms); }
 
 int vba_schur_outlier_power_att(vba_schur_handle h, double lamda, double ncp, double crit, double* mdb, double* ext_pos, double* ext_att,
                                 double* ext_lm, double* del_pos, double* del_lm, double* lm_mdb, double* lm_ext, double* lm_del_pos, double* pose_fit,
@@ -262,10 +242,6 @@ int vba_schur_outlier_power_att(vba_schur_handle h, double lamda, double ncp, do
     return schur_power_call(h, kSchurAtt, lamda, ncp, crit, mdb, ext_pos, ext_att, ext_lm, del_pos, del_lm, lm_mdb, lm_ext, lm_del_pos, pose_fit, fit, info);
 }
 
-int vba_schur_last_outlier_power_att_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->pow.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_outlier_power_att_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::pow, ms); }
 
 }  // extern "C"

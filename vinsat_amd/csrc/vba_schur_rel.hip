@@ -1,14 +1,12 @@
-// vba_schur_rel.hip -- the reliability query of the free-landmark mode (vba_schur_reliability; include/vinsat_ba.h carries the
-// contract): the device part of the covariance query (vba_schur_cov.hip), then leverage and w-test of every row and of every
-// catalogue prior, the statistics per landmark and per pose, the totals of the fit.  Its device part is what vba_schur_snoop starts
-// with.  vba_schur_reliability_dyn, the query of a handle with the dynamics factor, follows it: the device part of
-// vba_schur_covariance_dyn, the same passes, then the leverage of every dynamics edge and the edges' share of the fit; its device
-// part is what vba_schur_snoop_dyn starts with.  vba_schur.hip carries the map of the units; the closed forms are
-// vba_schur_rel_math.h and vba_schur_dyn_rel.h; the gather of a row is vba_schur_rowpass.h, shared with the row pass of the outlier
-// power query (vba_schur_power.hip), which takes the place of k_rel_rows in the device part when that query runs it.
-// vba_schur_reliability_att, the query of a handle with the attitude factor too, follows vba_schur_reliability_dyn in the same way:
-// its launches in their order, then leverage and w-test of every attitude edge (vba_schur_att_rel.h) and the edges' share of the fit;
-// its device part is what vba_schur_snoop_att and vba_schur_outlier_power_att start with.
+// vba_schur_rel.hip -- the reliability query of the free-landmark mode (vba_schur_reliability, vba_schur_reliability_dyn on a handle
+// with the dynamics factor, vba_schur_reliability_att on one with the attitude factor too; include/vinsat_ba.h carries the contracts):
+// the device part of the covariance query (vba_schur_cov.hip), then leverage and w-test of every row and of every catalogue prior, the
+// statistics per landmark and per pose, the totals of the fit; with the dynamics factor the leverage of every dynamics edge and the
+// edges' share of the fit (vba_schur_dyn_rel.h); with the attitude factor leverage and w-test of every attitude edge and their share
+// (vba_schur_att_rel.h).  One body (schur_rel_call) and one device part (schur_rel_device) serve the three kinds of handle; the device
+// part is what the snoop and the outlier power queries start with (the row pass of the latter, vba_schur_power.hip, takes the place of
+// k_rel_rows there).  vba_schur.hip carries the map of the units; the closed forms of the rows are vba_schur_rel_math.h, the gather of
+// a row is vba_schur_rowpass.h.
 #include "vba_schur_context.h"
 #include "vba_schur_att_rel.h"
 #include "vba_schur_dyn_rel.h"
@@ -224,13 +222,6 @@ __global__ __launch_bounds__(256) void k_rel_att_totals(int n, int L, const doub
 
 }  // namespace
 
-int schur_kind_check(SchurKind kind, vba_schur_handle h, const char* dyn_entry) {
-    if (kind != kSchurPlain && !h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
-    if (kind == kSchurAtt && !h->att.enabled) return sfail(VBA_ESTATE, "the attitude factor is not enabled on this handle");
-    if (kind != kSchurAtt && h->att.enabled) return sfail(VBA_ESTATE, std::string(dyn_entry) + kAttRefusal);
-    return VBA_OK;
-}
-
 // first reliability query of a handle: its scratch and its two timing events
 int schur_rel_alloc(vba_schur_handle h) {
     SchurRel& R = h->rel;
@@ -251,11 +242,14 @@ int schur_rel_alloc(vba_schur_handle h) {
     return VBA_OK;
 }
 
-// The device part of vba_schur_reliability, shared with vba_schur_snoop: schur_query_device with the landmark marginals from
-// ev_begin on, and unless the factorisation failed (*bad != 0: nothing more is launched) the three passes into the reliability
-// scratch.  The launches and their order are those vba_schur_reliability has always issued.  pow_ncp > 0
+// The device part of the reliability query of a handle of this kind, shared with the snoop and the outlier power queries:
+// schur_query_device with the landmark marginals from ev_begin on, and unless the factorisation failed (*bad != 0: nothing more is
+// launched) the passes into the reliability scratch -- rows, statistics, totals; with the dynamics factor the edge pass in front of
+// the totals and the edges folded into them behind (their cost shares are the ecost of the query's own build); with the attitude
+// factor then the attitude edge pass and those edges folded in (on such a handle the covariance query's build fills att.q_a, att.q_J,
+// att.q_ecost).  The launches and their order are those the three queries have always issued.  pow_ncp > 0
 // (vba_schur_outlier_power): the row pass is k_pow_rows, which leaves lev, wt, om as k_rel_rows does and that query's row figures.
-int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp) {
+int schur_rel_device(vba_schur_handle h, SchurKind kind, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp) {
     SchurQuery& Q = h->q;
     SchurRel& R = h->rel;
     hipStream_t s = h->stream;
@@ -266,44 +260,41 @@ int schur_rel_device(vba_schur_handle h, double lamda, hipEvent_t ev_begin, Schu
     else hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
     hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
                        R.pose_stats);
+    if (kind >= kSchurDyn)
+        hipLaunchKernelGGL(k_rel_edges, dim3(((V.n - 1) * kEdgeLanes + 255) / 256), dim3(256), 0, s, V.n, h->dyn.sigma, Q.dyn_A, Q.state, Q.edge, R.elev);
     hipLaunchKernelGGL(k_rel_totals, dim3(1), dim3(256), 0, s, V, R.lev, R.wt, R.om, R.lmlev, R.lmwt, R.lmom, R.fit);
+    if (kind >= kSchurDyn) hipLaunchKernelGGL(k_rel_edge_totals, dim3(1), dim3(256), 0, s, V.n, V.L, R.elev, Q.dyn_ecost, R.fit);
+    if (kind == kSchurAtt) {
+        hipLaunchKernelGGL(k_rel_att_edges, dim3((V.n - 1 + 255) / 256), dim3(256), 0, s, V.n, h->att.sigma, h->att.q_J, h->att.q_a, Q.state, Q.edge,
+                           R.alev, R.awt);
+        hipLaunchKernelGGL(k_rel_att_totals, dim3(1), dim3(256), 0, s, V.n, V.L, R.alev, h->att.q_ecost, R.awt, R.fit);
+    }
     return VBA_OK;
 }
 
-// The device part of vba_schur_reliability_dyn, shared with vba_schur_snoop_dyn: schur_query_device_dyn with the landmark marginals
-// from ev_begin on, and unless the factorisation failed the row and statistics passes as the plain query runs them, the edge pass,
-// the totals of the plain query and the edges folded into them.  The edges' cost shares are the ecost of the query's own build.
-// pow_ncp as in schur_rel_device.
-int schur_rel_device_dyn(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp) {
-    SchurQuery& Q = h->q;
+// The body of the three entries behind their null check (and the kind check of the plain one): the six outputs of every kind, the
+// edges' two with the dynamics factor, the attitude edges' three with the attitude factor, the fit of 8, 10 or 13 slots.
+static int schur_rel_call(vba_schur_handle h, SchurKind kind, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
+                          double* lm_stats, double* pose_stats, double* edge_leverage, double* edge_omega, double* att_leverage, double* att_wtest,
+                          double* att_omega, double* fit, int* info) {
+    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
+    if (int rc = schur_query_begin(h, kind, kind == kSchurPlain ? "vba_schur_reliability" : "vba_schur_reliability_dyn")) return rc;
+    if (int rc = schur_rel_alloc(h)) return rc;
     SchurRel& R = h->rel;
-    hipStream_t s = h->stream;
-    if (int rc = schur_query_device_dyn(h, lamda, true, ev_begin, V, bad)) return rc;
-    if (*bad != 0) return VBA_OK;
-    if (pow_ncp > 0.0) schur_pow_rows_launch(h, V, pow_ncp);
-    else hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)(((size_t)V.m + 255) / 256)), dim3(256), 0, s, V, Q.pair, Q.lp_ptr, Q.lp_blk, Q.lm, R.lev, R.wt, R.om);
-    hipLaunchKernelGGL(k_rel_stats, dim3((std::max(V.L, V.n) + 255) / 256), dim3(256), 0, s, V, Q.lm, R.lev, R.wt, R.lmlev, R.lmwt, R.lmom, R.lm_stats,
-                       R.pose_stats);
-    hipLaunchKernelGGL(k_rel_edges, dim3(((V.n - 1) * kEdgeLanes + 255) / 256), dim3(256), 0, s, V.n, h->dyn.sigma, Q.dyn_A, Q.state, Q.edge, R.elev);
-    hipLaunchKernelGGL(k_rel_totals, dim3(1), dim3(256), 0, s, V, R.lev, R.wt, R.om, R.lmlev, R.lmwt, R.lmom, R.fit);
-    hipLaunchKernelGGL(k_rel_edge_totals, dim3(1), dim3(256), 0, s, V.n, V.L, R.elev, Q.dyn_ecost, R.fit);
-    return VBA_OK;
-}
-
-// The device part of vba_schur_reliability_att, shared with vba_schur_snoop_att and vba_schur_outlier_power_att:
-// schur_rel_device_dyn's launches in their order (on a handle with the attitude factor the covariance query's build includes it and
-// fills att.q_a, att.q_J, att.q_ecost), then the attitude edge pass and the attitude edges folded into the fit.  pow_ncp as in
-// schur_rel_device.
-int schur_rel_device_att(vba_schur_handle h, double lamda, hipEvent_t ev_begin, SchurView& V, int* bad, double pow_ncp) {
-    SchurQuery& Q = h->q;
-    SchurRel& R = h->rel;
-    hipStream_t s = h->stream;
-    if (int rc = schur_rel_device_dyn(h, lamda, ev_begin, V, bad, pow_ncp)) return rc;
-    if (*bad != 0) return VBA_OK;
-    hipLaunchKernelGGL(k_rel_att_edges, dim3((V.n - 1 + 255) / 256), dim3(256), 0, s, V.n, h->att.sigma, h->att.q_J, h->att.q_a, Q.state, Q.edge, R.alev,
-                       R.awt);
-    hipLaunchKernelGGL(k_rel_att_totals, dim3(1), dim3(256), 0, s, V.n, V.L, R.alev, h->att.q_ecost, R.awt, R.fit);
-    return VBA_OK;
+    SchurView V;
+    int bad = 0;
+    if (int rc = schur_rel_device(h, kind, lamda, R.sc.ev[0], V, &bad)) return rc;
+    *info = bad;
+    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
+    Out outs[12] = {{leverage, R.lev, m}, {wtest, R.wt, m}, {lm_leverage, R.lmlev, L}, {lm_wtest, R.lmwt, L}, {lm_stats, R.lm_stats, 3 * L},
+                    {pose_stats, R.pose_stats, 3 * n}};
+    size_t count = 6;
+    if (kind >= kSchurDyn) { outs[count++] = {edge_leverage, R.elev, n - 1}; outs[count++] = {edge_omega, h->q.dyn_ecost, n - 1}; }
+    if (kind == kSchurAtt) {
+        outs[count++] = {att_leverage, R.alev, n - 1}; outs[count++] = {att_wtest, R.awt, n - 1}; outs[count++] = {att_omega, h->att.q_ecost, n - 1};
+    }
+    outs[count++] = {fit, R.fit, kind == kSchurAtt ? (size_t)13 : kind == kSchurDyn ? (size_t)10 : (size_t)8};
+    return schur_outputs_finish(R.sc, h->stream, bad, outs, count);
 }
 
 extern "C" {
@@ -312,117 +303,29 @@ int vba_schur_reliability_att(vba_schur_handle h, double lamda, double* leverage
                               double* lm_stats, double* pose_stats, double* edge_leverage, double* edge_omega, double* att_leverage,
                               double* att_wtest, double* att_omega, double* fit, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
-    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    if (int rc = schur_kind_check(kSchurAtt, h, "vba_schur_reliability_dyn")) return rc;
-    SCHK(hipSetDevice(h->device));
-    if (int rc = schur_query_alloc(h)) return rc;
-    if (int rc = schur_query_index(h)) return rc;
-    if (int rc = schur_rel_alloc(h)) return rc;
-    SchurRel& R = h->rel;
-    hipStream_t s = h->stream;
-    SchurView V;
-    int bad = 0;
-    if (int rc = schur_rel_device_att(h, lamda, R.sc.ev[0], V, &bad)) return rc;
-    *info = bad;
-    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
-    struct Out { double* host; const double* dev; size_t count; };
-    const Out outs[12] = {{leverage, R.lev, m}, {wtest, R.wt, m}, {lm_leverage, R.lmlev, L}, {lm_wtest, R.lmwt, L}, {lm_stats, R.lm_stats, 3 * L},
-                          {pose_stats, R.pose_stats, 3 * n}, {edge_leverage, R.elev, n - 1}, {edge_omega, h->q.dyn_ecost, n - 1},
-                          {att_leverage, R.alev, n - 1}, {att_wtest, R.awt, n - 1}, {att_omega, h->att.q_ecost, n - 1}, {fit, R.fit, 13}};
-    if (bad != 0) {                 // no factor, no covariance, no test: NaN, and the row in *info
-        if (int rc = schur_scratch_finish(R.sc, s)) return rc;
-        for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
-        return VBA_OK;
-    }
-    return schur_scratch_finish(R.sc, s, [&]() -> int {
-        SCHK(hipGetLastError());
-        for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
-        return VBA_OK;
-    });
+    return schur_rel_call(h, kSchurAtt, lamda, leverage, wtest, lm_leverage, lm_wtest, lm_stats, pose_stats, edge_leverage, edge_omega, att_leverage,
+                          att_wtest, att_omega, fit, info);
 }
 
-int vba_schur_last_reliability_att_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->rel.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_reliability_att_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::rel, ms); }
 
 int vba_schur_reliability_dyn(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
                               double* lm_stats, double* pose_stats, double* edge_leverage, double* edge_omega, double* fit, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
-    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    if (!h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
-    if (h->att.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_reliability_dyn") + kAttRefusal);
-    SCHK(hipSetDevice(h->device));
-    if (int rc = schur_query_alloc(h)) return rc;
-    if (int rc = schur_query_index(h)) return rc;
-    if (int rc = schur_rel_alloc(h)) return rc;
-    SchurRel& R = h->rel;
-    hipStream_t s = h->stream;
-    SchurView V;
-    int bad = 0;
-    if (int rc = schur_rel_device_dyn(h, lamda, R.sc.ev[0], V, &bad)) return rc;
-    *info = bad;
-    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
-    struct Out { double* host; const double* dev; size_t count; };
-    const Out outs[9] = {{leverage, R.lev, m}, {wtest, R.wt, m}, {lm_leverage, R.lmlev, L}, {lm_wtest, R.lmwt, L}, {lm_stats, R.lm_stats, 3 * L},
-                         {pose_stats, R.pose_stats, 3 * n}, {edge_leverage, R.elev, n - 1}, {edge_omega, h->q.dyn_ecost, n - 1}, {fit, R.fit, 10}};
-    if (bad != 0) {                 // no factor, no covariance, no test: NaN, and the row in *info
-        if (int rc = schur_scratch_finish(R.sc, s)) return rc;
-        for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
-        return VBA_OK;
-    }
-    return schur_scratch_finish(R.sc, s, [&]() -> int {
-        SCHK(hipGetLastError());
-        for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
-        return VBA_OK;
-    });
+    return schur_rel_call(h, kSchurDyn, lamda, leverage, wtest, lm_leverage, lm_wtest, lm_stats, pose_stats, edge_leverage, edge_omega, nullptr, nullptr,
+                          nullptr, fit, info);
 }
 
-int vba_schur_last_reliability_dyn_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->rel.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_reliability_dyn_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::rel, ms); }
 
 int vba_schur_reliability(vba_schur_handle h, double lamda, double* leverage, double* wtest, double* lm_leverage, double* lm_wtest,
                           double* lm_stats, double* pose_stats, double* fit, int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_reliability") + kDynRefusal);
-    if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
-    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    SCHK(hipSetDevice(h->device));
-    if (int rc = schur_query_alloc(h)) return rc;
-    if (int rc = schur_query_index(h)) return rc;
-    if (int rc = schur_rel_alloc(h)) return rc;
-    SchurRel& R = h->rel;
-    hipStream_t s = h->stream;
-    SchurView V;
-    int bad = 0;
-    if (int rc = schur_rel_device(h, lamda, R.sc.ev[0], V, &bad)) return rc;
-    *info = bad;
-    const size_t m = (size_t)V.m, L = (size_t)V.L, n = (size_t)V.n;
-    struct Out { double* host; const double* dev; size_t count; };
-    const Out outs[7] = {{leverage, R.lev, m}, {wtest, R.wt, m}, {lm_leverage, R.lmlev, L}, {lm_wtest, R.lmwt, L}, {lm_stats, R.lm_stats, 3 * L},
-                         {pose_stats, R.pose_stats, 3 * n}, {fit, R.fit, 8}};
-    if (bad != 0) {                 // no factor, no covariance, no test: NaN, and the row in *info
-        if (int rc = schur_scratch_finish(R.sc, s)) return rc;
-        for (const Out& o : outs) if (o.host) std::fill(o.host, o.host + o.count, std::nan(""));
-        return VBA_OK;
-    }
-    return schur_scratch_finish(R.sc, s, [&]() -> int {
-        SCHK(hipGetLastError());
-        for (const Out& o : outs) if (o.host) SCHK(hipMemcpyAsync(o.host, o.dev, o.count * 8, hipMemcpyDeviceToHost, s));
-        return VBA_OK;
-    });
+    if (int rc = schur_kind_check(kSchurPlain, h, "vba_schur_reliability")) return rc;
+    return schur_rel_call(h, kSchurPlain, lamda, leverage, wtest, lm_leverage, lm_wtest, lm_stats, pose_stats, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          fit, info);
 }
 
-int vba_schur_last_reliability_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->rel.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_reliability_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::rel, ms); }
 
 }  // extern "C"

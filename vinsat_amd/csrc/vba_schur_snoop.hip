@@ -169,18 +169,14 @@ static int schur_snoop_call(vba_schur_handle h, SchurKind kind, double lamda, do
     if (!(lamda >= 0.0)) return sfail(VBA_EINVAL, "lamda must be >= 0");
     if (!(crit >= 0.0)) return sfail(VBA_EINVAL, "crit must be >= 0 (+inf rejects nothing)");
     if (min_rows < 0 || min_track < 0) return sfail(VBA_EINVAL, "min_rows and min_track must be >= 0");
-    if (!h->uploaded || !h->have_state) return sfail(VBA_ESTATE, "upload the problem and set the state first");
-    if (int rc = schur_kind_check(kind, h, "vba_schur_snoop_dyn")) return rc;
-    SCHK(hipSetDevice(h->device));
-    if (int rc = schur_query_alloc(h)) return rc;
-    if (int rc = schur_query_index(h)) return rc;
+    if (int rc = schur_query_begin(h, kind, kind == kSchurPlain ? "vba_schur_snoop" : "vba_schur_snoop_dyn")) return rc;
     if (int rc = schur_rel_alloc(h)) return rc;
     if (int rc = schur_snoop_alloc(h)) return rc;
     SchurSnoop& Z = h->snoop;
     hipStream_t s = h->stream;
     SchurView V;
     int bad = 0;
-    if (int rc = schur_rel_device_of(kind, h, lamda, Z.sc.ev[0], V, &bad)) return rc;
+    if (int rc = schur_rel_device(h, kind, lamda, Z.sc.ev[0], V, &bad)) return rc;
     *info = bad;
     if (counts) counts[0] = counts[1] = counts[2] = 0;
     if (bad != 0) {                 // no factor, no test: nothing is rejected; the critical value of a fit that does not exist
@@ -222,7 +218,7 @@ extern "C" {
 int vba_schur_snoop(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
                     int* info) {
     if (!h || !info) return sfail(VBA_EINVAL, "null argument");
-    if (h->dyn.enabled) return sfail(VBA_ESTATE, std::string("vba_schur_snoop") + kDynRefusal);
+    if (int rc = schur_kind_check(kSchurPlain, h, "vba_schur_snoop")) return rc;
     return schur_snoop_call(h, kSchurPlain, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
 }
 
@@ -232,11 +228,7 @@ int vba_schur_snoop_dyn(vba_schur_handle h, double lamda, double crit, int scale
     return schur_snoop_call(h, kSchurDyn, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
 }
 
-int vba_schur_last_snoop_dyn_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->snoop.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_snoop_dyn_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::snoop, ms); }
 
 int vba_schur_snoop_att(vba_schur_handle h, double lamda, double crit, int scaled, int min_rows, int min_track, int* counts, double* crit_used,
                         int* info) {
@@ -244,11 +236,7 @@ int vba_schur_snoop_att(vba_schur_handle h, double lamda, double crit, int scale
     return schur_snoop_call(h, kSchurAtt, lamda, crit, scaled, min_rows, min_track, counts, crit_used, info);
 }
 
-int vba_schur_last_snoop_att_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->snoop.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_snoop_att_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::snoop, ms); }
 
 int vba_schur_rejected(vba_schur_handle h, unsigned char* row_mask, unsigned char* lm_mask, int* totals) {
     if (!h) return sfail(VBA_EINVAL, "null handle");
@@ -279,10 +267,6 @@ int vba_schur_snoop_restore(vba_schur_handle h) {
     return VBA_OK;
 }
 
-int vba_schur_last_snoop_ms(vba_schur_handle h, float* ms) {
-    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
-    *ms = h->snoop.sc.ms;
-    return VBA_OK;
-}
+int vba_schur_last_snoop_ms(vba_schur_handle h, float* ms) { return schur_last_ms(h, &vba_schur_context::snoop, ms); }
 
 }  // extern "C"

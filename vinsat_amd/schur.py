@@ -279,9 +279,7 @@ class SchurBA:
         return out
 
     def last_covariance_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_covariance_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_covariance_ms")
 
     def state_covariance(self, lamda=0.0, pairs=False, strict=True):
         """``vba_schur_covariance_dyn`` at the resident state of a handle with the dynamics factor (``include/vinsat_ba.h``):
@@ -309,9 +307,7 @@ class SchurBA:
         return out
 
     def last_state_covariance_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_covariance_dyn_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_covariance_dyn_ms")
 
     def reliability(self, lamda=0.0, strict=True):
         """``vba_schur_reliability`` at the resident state (``include/vinsat_ba.h``): which row, and which catalogue position,
@@ -322,26 +318,10 @@ class SchurBA:
         Up to the variance factor of the weights (``fit["s0sq"]`` estimates it).  Nothing on the handle changes.
 
         ``strict`` as in :meth:`covariance`: a system that is not positive definite raises, or gives NaN everywhere."""
-        out = dict(leverage=np.empty(self.m), wtest=np.empty(self.m), lm_leverage=np.empty(self.L), lm_wtest=np.empty(self.L),
-                   lm_stats=np.empty((self.L, 3)), pose_stats=np.empty((self.n, 3)))
-        fit, info = np.empty(len(FIT_NAMES)), c_int()
-        self._check(self.lib.vba_schur_reliability(self.h, float(lamda), *[a.ctypes.data_as(PD) for a in out.values()], fit.ctypes.data_as(PD),
-                                                   byref(info)))
-        if info.value != 0 and strict:
-            raise _lib.VbaError(f"schur reliability: the reduced camera system is not positive definite at lamda = {lamda:g} "
-                                f"(non-positive pivot at row {info.value - 1})")
-        for key in ("leverage", "wtest"):               # device rows are sorted by landmark: back to the caller's order
-            back = np.empty(self.m)
-            back[self.order] = out[key]
-            out[key] = back
-        out["fit"] = dict(zip(FIT_NAMES, fit.tolist()))
-        out["info"] = info.value
-        return out
+        return self._reliability("plain", lamda, strict)
 
     def last_reliability_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_reliability_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_reliability_ms")
 
     def snoop(self, lamda=0.0, crit=3.29, scaled=True, min_rows=6, min_track=3, strict=True):
         """``vba_schur_snoop`` at the resident state (``include/vinsat_ba.h`` states the rule): the device part of
@@ -353,13 +333,7 @@ class SchurBA:
         ``crit_used``, ``info``.  :meth:`rejected` gives the cumulative masks, :meth:`restore_rejected` undoes everything.
 
         ``strict`` as in :meth:`reliability`: a system that is not positive definite raises, or rejects nothing and tells ``info``."""
-        counts, used, info = (c_int * 3)(), c_double(), c_int()
-        self._check(self.lib.vba_schur_snoop(self.h, float(lamda), float(crit), int(bool(scaled)), int(min_rows), int(min_track), counts,
-                                             byref(used), byref(info)))
-        if info.value != 0 and strict:
-            raise _lib.VbaError(f"schur snoop: the reduced camera system is not positive definite at lamda = {lamda:g} "
-                                f"(non-positive pivot at row {info.value - 1})")
-        return dict(rows=counts[0], landmarks=counts[1], rows_via_landmarks=counts[2], crit_used=used.value, info=info.value)
+        return self._snoop("plain", lamda, crit, scaled, min_rows, min_track, strict)
 
     def rejected(self):
         """``(row_mask [m] bool in the CALLER's row order, landmark_mask [L] bool)``: everything :meth:`snoop` rejected on this
@@ -375,9 +349,7 @@ class SchurBA:
         self._check(self.lib.vba_schur_snoop_restore(self.h))
 
     def last_snoop_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_snoop_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_snoop_ms")
 
     def state_reliability(self, lamda=0.0, strict=True):
         """``vba_schur_reliability_dyn`` at the resident state of a handle with the dynamics factor (``include/vinsat_ba.h``): the
@@ -390,70 +362,84 @@ class SchurBA:
         ``strict`` as in :meth:`state_covariance`.  A handle without the dynamics factor raises: :meth:`reliability` is its query.
         A handle with the attitude factor raises too, as do :meth:`state_snoop` and :meth:`state_outlier_power`: their redundancy
         counts and edge leverages do not know the attitude equations."""
-        ne = max(self.n - 1, 0)
-        out = dict(leverage=np.empty(self.m), wtest=np.empty(self.m), lm_leverage=np.empty(self.L), lm_wtest=np.empty(self.L),
-                   lm_stats=np.empty((self.L, 3)), pose_stats=np.empty((self.n, 3)), edge_leverage=np.empty(ne), edge_omega=np.empty(ne))
-        fit, info = np.empty(len(FIT_NAMES_DYN)), c_int()
-        self._check(self.lib.vba_schur_reliability_dyn(self.h, float(lamda), *[a.ctypes.data_as(PD) for a in out.values()],
-                                                       fit.ctypes.data_as(PD), byref(info)))
-        if info.value != 0 and strict:
-            raise _lib.VbaError(f"schur state reliability: the reduced system is not positive definite at lamda = {lamda:g} "
-                                f"(non-positive pivot at row {info.value - 1})")
-        for key in ("leverage", "wtest"):               # device rows are sorted by landmark: back to the caller's order
-            back = np.empty(self.m)
-            back[self.order] = out[key]
-            out[key] = back
-        out["fit"] = dict(zip(FIT_NAMES_DYN, fit.tolist()))
-        out["info"] = info.value
-        return out
+        return self._reliability("state", lamda, strict)
 
     def last_state_reliability_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_reliability_dyn_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_reliability_dyn_ms")
 
     def state_snoop(self, lamda=0.0, crit=3.29, scaled=True, min_rows=6, min_track=3, strict=True):
         """``vba_schur_snoop_dyn``: :meth:`snoop` on a handle with the dynamics factor -- the same rule, arguments and result, fed
         by the device part of :meth:`state_reliability`.  Edges are never rejected; :meth:`rejected` and :meth:`restore_rejected`
         serve both."""
-        counts, used, info = (c_int * 3)(), c_double(), c_int()
-        self._check(self.lib.vba_schur_snoop_dyn(self.h, float(lamda), float(crit), int(bool(scaled)), int(min_rows), int(min_track), counts,
-                                                 byref(used), byref(info)))
-        if info.value != 0 and strict:
-            raise _lib.VbaError(f"schur state snoop: the reduced system is not positive definite at lamda = {lamda:g} "
-                                f"(non-positive pivot at row {info.value - 1})")
-        return dict(rows=counts[0], landmarks=counts[1], rows_via_landmarks=counts[2], crit_used=used.value, info=info.value)
+        return self._snoop("state", lamda, crit, scaled, min_rows, min_track, strict)
 
     def last_state_snoop_ms(self):
+        return self._last_ms("vba_schur_last_snoop_dyn_ms")
+
+    # Kind of handle -- the plain one, one with the dynamics factor, one with the attitude factor too -> what its three uncertainty queries
+    # differ in: the fit names of its reliability query, that query's arrays beyond the common six (each [n - 1]), the suffix of its C
+    # entries (vba_schur_reliability<suffix>, vba_schur_snoop<suffix>, vba_schur_outlier_power<suffix>), the label of its error messages,
+    # and what the messages of its reliability query and its snoop call the system.
+    _KINDS = {"plain": (FIT_NAMES, (), "", "", "reduced camera system"),
+              "state": (FIT_NAMES_DYN, ("edge_leverage", "edge_omega"), "_dyn", "state ", "reduced system"),
+              "attitude": (FIT_NAMES_ATT, ("edge_leverage", "edge_omega", "att_leverage", "att_wtest", "att_omega"), "_att", "attitude ", "reduced system")}
+
+    def _last_ms(self, entry_name):
+        """The milliseconds one of the ``vba_schur_last_*_ms`` entries reports."""
         v = c_float()
-        self._check(self.lib.vba_schur_last_snoop_dyn_ms(self.h, byref(v)))
+        self._check(getattr(self.lib, entry_name)(self.h, byref(v)))
         return v.value
 
-    # kind of handle -> (leading fit names, entry, label of the error message) of the outlier power query
-    _POWER_KINDS = {"plain": (FIT_NAMES, "vba_schur_outlier_power", ""), "state": (FIT_NAMES_DYN, "vba_schur_outlier_power_dyn", "state "),
-                    "attitude": (FIT_NAMES_ATT, "vba_schur_outlier_power_att", "attitude ")}
+    def _not_positive_definite(self, what, system, lamda, info):
+        return _lib.VbaError(f"schur {what}: the {system} is not positive definite at lamda = {lamda:g} (non-positive pivot at row {info - 1})")
+
+    def _finish(self, out, row_keys, names, fit, info):
+        """Rows back to the caller's order (device rows are sorted by landmark), ``fit`` as a dict of ``names``, ``info``."""
+        for key in row_keys:
+            back = np.empty(self.m)
+            back[self.order] = out[key]
+            out[key] = back
+        out["fit"] = dict(zip(names, fit.tolist()))
+        out["info"] = info
+        return out
+
+    def _reliability(self, kind, lamda, strict):
+        """``kind``: a key of ``_KINDS``."""
+        names, extra, suffix, label, system = self._KINDS[kind]
+        out = dict(leverage=np.empty(self.m), wtest=np.empty(self.m), lm_leverage=np.empty(self.L), lm_wtest=np.empty(self.L),
+                   lm_stats=np.empty((self.L, 3)), pose_stats=np.empty((self.n, 3)))
+        out.update({k: np.empty(max(self.n - 1, 0)) for k in extra})
+        fit, info = np.empty(len(names)), c_int()
+        entry = getattr(self.lib, "vba_schur_reliability" + suffix)
+        self._check(entry(self.h, float(lamda), *[a.ctypes.data_as(PD) for a in out.values()], fit.ctypes.data_as(PD), byref(info)))
+        if info.value != 0 and strict:
+            raise self._not_positive_definite(label + "reliability", system, lamda, info.value)
+        return self._finish(out, ("leverage", "wtest"), names, fit, info.value)
+
+    def _snoop(self, kind, lamda, crit, scaled, min_rows, min_track, strict):
+        """``kind``: a key of ``_KINDS``."""
+        _, _, suffix, label, system = self._KINDS[kind]
+        counts, used, info = (c_int * 3)(), c_double(), c_int()
+        entry = getattr(self.lib, "vba_schur_snoop" + suffix)
+        self._check(entry(self.h, float(lamda), float(crit), int(bool(scaled)), int(min_rows), int(min_track), counts, byref(used), byref(info)))
+        if info.value != 0 and strict:
+            raise self._not_positive_definite(label + "snoop", system, lamda, info.value)
+        return dict(rows=counts[0], landmarks=counts[1], rows_via_landmarks=counts[2], crit_used=used.value, info=info.value)
 
     def _outlier_power(self, kind, lamda, ncp, crit, strict):
-        """``kind``: a key of ``_POWER_KINDS`` -- the plain handle, one with the dynamics factor, one with the attitude factor too."""
-        lead, entry_name, label = self._POWER_KINDS[kind]
+        """``kind``: a key of ``_KINDS``."""
+        lead, _, suffix, label, _ = self._KINDS[kind]
         names = lead + POWER_FIT_NAMES
         out = {k: np.empty(self.m) for k in POWER_ROW_KEYS}
         out.update({k: np.empty(self.L) for k in POWER_LM_KEYS})
         out["pose_fit"] = np.empty((self.n, 4))
         fit, info = np.empty(len(names)), c_int()
-        entry = getattr(self.lib, entry_name)
+        entry = getattr(self.lib, "vba_schur_outlier_power" + suffix)
         self._check(entry(self.h, float(lamda), float(ncp), float(crit), *[a.ctypes.data_as(PD) for a in out.values()], fit.ctypes.data_as(PD),
                           byref(info)))
         if info.value != 0 and strict:
-            raise _lib.VbaError(f"schur {label}outlier power: the reduced system is not positive definite at lamda = {lamda:g} "
-                                f"(non-positive pivot at row {info.value - 1})")
-        for key in POWER_ROW_KEYS:                      # device rows are sorted by landmark: back to the caller's order
-            back = np.empty(self.m)
-            back[self.order] = out[key]
-            out[key] = back
-        out["fit"] = dict(zip(names, fit.tolist()))
-        out["info"] = info.value
-        return out
+            raise self._not_positive_definite(label + "outlier power", "reduced system", lamda, info.value)
+        return self._finish(out, POWER_ROW_KEYS, names, fit, info.value)
 
     def outlier_power(self, lamda=0.0, ncp=17.075, crit=3.29, strict=True):
         """``vba_schur_outlier_power`` at the resident state (``include/vinsat_ba.h`` defines every figure): how large an error in a
@@ -470,9 +456,7 @@ class SchurBA:
         return self._outlier_power("plain", lamda, ncp, crit, strict)
 
     def last_outlier_power_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_outlier_power_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_outlier_power_ms")
 
     def state_outlier_power(self, lamda=0.0, ncp=17.075, crit=3.29, strict=True):
         """``vba_schur_outlier_power_dyn``: the dict of :meth:`outlier_power` on a handle with the dynamics factor, every figure from
@@ -481,9 +465,7 @@ class SchurBA:
         return self._outlier_power("state", lamda, ncp, crit, strict)
 
     def last_state_outlier_power_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_outlier_power_dyn_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_outlier_power_dyn_ms")
 
     def attitude_reliability(self, lamda=0.0, strict=True):
         """``vba_schur_reliability_att`` at the resident state of a handle with the dynamics AND the attitude factor
@@ -496,46 +478,20 @@ class SchurBA:
 
         ``strict`` as in :meth:`state_covariance`.  A handle without the attitude factor raises: :meth:`state_reliability` or
         :meth:`reliability` is its query."""
-        ne = max(self.n - 1, 0)
-        out = dict(leverage=np.empty(self.m), wtest=np.empty(self.m), lm_leverage=np.empty(self.L), lm_wtest=np.empty(self.L),
-                   lm_stats=np.empty((self.L, 3)), pose_stats=np.empty((self.n, 3)), edge_leverage=np.empty(ne), edge_omega=np.empty(ne),
-                   att_leverage=np.empty(ne), att_wtest=np.empty(ne), att_omega=np.empty(ne))
-        fit, info = np.empty(len(FIT_NAMES_ATT)), c_int()
-        self._check(self.lib.vba_schur_reliability_att(self.h, float(lamda), *[a.ctypes.data_as(PD) for a in out.values()],
-                                                       fit.ctypes.data_as(PD), byref(info)))
-        if info.value != 0 and strict:
-            raise _lib.VbaError(f"schur attitude reliability: the reduced system is not positive definite at lamda = {lamda:g} "
-                                f"(non-positive pivot at row {info.value - 1})")
-        for key in ("leverage", "wtest"):               # device rows are sorted by landmark: back to the caller's order
-            back = np.empty(self.m)
-            back[self.order] = out[key]
-            out[key] = back
-        out["fit"] = dict(zip(FIT_NAMES_ATT, fit.tolist()))
-        out["info"] = info.value
-        return out
+        return self._reliability("attitude", lamda, strict)
 
     def last_attitude_reliability_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_reliability_att_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_reliability_att_ms")
 
     def attitude_snoop(self, lamda=0.0, crit=3.29, scaled=True, min_rows=6, min_track=3, strict=True):
         """``vba_schur_snoop_att``: :meth:`snoop` on a handle with both factors -- the same rule, arguments and result, fed by the
         device part of :meth:`attitude_reliability` (``scaled`` reads its ``s0sq``, which counts the attitude equations).  Edges of
         either kind are never rejected: a gyro suspect is reported (:func:`gyro_suspects`), not acted on.  :meth:`rejected` and
         :meth:`restore_rejected` serve it too."""
-        counts, used, info = (c_int * 3)(), c_double(), c_int()
-        self._check(self.lib.vba_schur_snoop_att(self.h, float(lamda), float(crit), int(bool(scaled)), int(min_rows), int(min_track), counts,
-                                                 byref(used), byref(info)))
-        if info.value != 0 and strict:
-            raise _lib.VbaError(f"schur attitude snoop: the reduced system is not positive definite at lamda = {lamda:g} "
-                                f"(non-positive pivot at row {info.value - 1})")
-        return dict(rows=counts[0], landmarks=counts[1], rows_via_landmarks=counts[2], crit_used=used.value, info=info.value)
+        return self._snoop("attitude", lamda, crit, scaled, min_rows, min_track, strict)
 
     def last_attitude_snoop_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_snoop_att_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_snoop_att_ms")
 
     def attitude_outlier_power(self, lamda=0.0, ncp=17.075, crit=3.29, strict=True):
         """``vba_schur_outlier_power_att``: the dict of :meth:`outlier_power` on a handle with both factors, every figure from the
@@ -544,9 +500,7 @@ class SchurBA:
         return self._outlier_power("attitude", lamda, ncp, crit, strict)
 
     def last_attitude_outlier_power_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_outlier_power_att_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_outlier_power_att_ms")
 
     def reweight(self, alpha):
         """``vba_schur_reweight`` at the resident state (``include/vinsat_ba.h``): the reference's robust weights
@@ -573,9 +527,7 @@ class SchurBA:
         return out.reshape(self.m, 2)
 
     def last_reweight_ms(self):
-        v = c_float()
-        self._check(self.lib.vba_schur_last_reweight_ms(self.h, byref(v)))
-        return v.value
+        return self._last_ms("vba_schur_last_reweight_ms")
 
     def solve(self, lamda0=1e-4, max_iters=20, tol=1e-10, snoop=None, robust=None, state_snoop=None, attitude_snoop=None):
         """Levenberg-Marquardt driver: damping x10 on a rejected trial, /10 on an accepted one.  Returns the cost history.
