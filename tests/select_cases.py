@@ -4,8 +4,9 @@ per session.
 
 The rows are drawn from one pool (``trial_cases.rich(16, 260)``: 4160 rows, states a tenth of the driver's perturbation off the truth)
 and measured anew: ``uv = O.landmark_project(states, ...) + delta``, so the keys of a call at ``states`` are |delta| to within ~1e-13
-(the device's projection rounds differently).  A group of rows that is to share the top 32 bits of its keys has the offset 2.7 (9.3 in
-``stale``) +- 1e-7: mixed low mantissa bits, so that neither the noise nor the jitter -- which makes the keys of the group differ, so
+(the device's projection rounds differently).  A group of rows that is to share the top 32 bits of its keys -- the bits KNOWN behind
+digit 2; the compacted list is keyed on fewer, ``key >> 42``, and every other row lies below 2 or above 3.5 px, outside the group's
+list under either reading -- has the offset 2.7 (9.3 in ``stale``) +- 1e-7: mixed low mantissa bits, so that neither the noise nor the jitter -- which makes the keys of the group differ, so
 that a select that returns a neighbour is seen -- carries into the compared bits.  A group that is to tie bit
 for bit -- also one call later, at other states -- is one row repeated (same landmark, pose and measurement) with confidence 0: its
 keys count in the median and it does not pull the step.  Copies of one row measured +- 1e-7 apart share their projection at every

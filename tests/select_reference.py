@@ -11,9 +11,16 @@ Restated from vba_device.h (tests/test_select_reference_host.py holds them again
   warm_range_start        ``lo`` for the median bits of the call in front (2^64 - 1: no range)
   SEL_BINS 2048, COUNT_LIMIT 1024 (a longer list is not ranked by counting), WARM_COUNT 192 (kWarmCount), SEL_ITEMS 8 (kSelItems)
 
-Branches (``select_finish_list``).  Exact select, list = the keys that share the median's top 32 bits (``key >> 31``):
+Branches (``select_finish_list``).  Exact select, list = the keys that ``k_select_pass<2, true>`` appends: those that match the digits
+known when it runs, 0 and 1 -- ``key >> sel_shift(1)`` = ``key >> LIST_SHIFT`` (42), the sign, the exponent and 10 bits of the mantissa.
+(Digit 2 is histogrammed by the same pass, so 32 bits are KNOWN once it has run; the list is the wider set.)
   count              list of <= 1024 keys: ranked by counting
-  digits             longer: digits 3, 4, 5 over the list
+  digits             longer: digit 2 from the pass's histogram, then digits 3, 4, 5 over the list
+Sharded mode (``predict_gathered``): the list has room for the 2 m_max keys of the rank's own slice and is filled from the gathered keys
+of all ranks, so it can overflow (cnt > 2 m_local; entries beyond the capacity are dropped by the append):
+  overflow-short     2 m_local < cnt <= 1024: digits 2 .. 5 over the gathered keys -- not a count over the truncated list
+  overflow-long      cnt > 1024 and > 2 m_local: the same fallback
+tests/test_gpu_sharded_stages.py runs all four on emulated ranks.
 Warm select, list = the keys of the warm bin of the wanted rank:
   subbin             <= 1024 keys: the top 8 bits of the offset inside the bin split them over 256 sub-bins, one is ranked
   long-first-digit   more: the first 11-bit digit of the offset, and its sub-bin (<= 1024 keys) is ranked by counting
@@ -34,8 +41,10 @@ SEL_ITEMS = 8
 SEL_ITEMS_BATCH = 32
 NO_RANGE = (1 << 64) - 1
 MASK64 = (1 << 64) - 1
+LIST_SHIFT = 42                 # sel_shift(1): the compacted list of the exact select holds the keys that agree above this bit
 MISSES = ("no-range", "below", "above", "full", "forced")
 EXACT_BRANCHES = ("count", "digits")
+GATHERED_BRANCHES = ("count", "digits", "overflow-short", "overflow-long")
 WARM_BRANCHES = ("subbin", "long-first-digit", "long-radix")
 
 
@@ -96,18 +105,56 @@ def _neighbours(ranked, r):
 
 # ------------------------------------------------------------------------------------------------ predictors
 def predict_exact(keys, m_max):
-    """The exact select on ``keys``: dict with ``cnt`` (keys sharing the median's top 32 bits, ``key >> 31``), ``rank`` (the wanted rank
-    among them), ``branch`` (``count`` / ``digits``), ``key`` and ``neighbours`` (see ``_neighbours``).  cnt > 2 m_max, the overflow
-    fallback, is impossible on an unsharded handle: asserted."""
+    """The exact select on ``keys``: dict with ``cnt`` (the list: keys agreeing with the median above bit ``LIST_SHIFT``), ``rank`` (the
+    wanted rank among them), ``branch`` (``count`` / ``digits``), ``key`` and ``neighbours`` (see ``_neighbours``).  All keys are the
+    handle's own here, at most 2 m_max, so the list cannot overflow (asserted); on a sharded handle it can: ``predict_gathered``,
+    tests/test_gpu_sharded_stages.py."""
+    p = predict_gathered(keys, m_max)
+    assert p["cnt"] <= 2 * m_max, "more keys than the handle has rows for: this is a gathered key set (predict_gathered)"
+    return p
+
+
+def predict_gathered(keys, m_local, shift=LIST_SHIFT):
+    """The exact select over the 2 m gathered ``keys`` of all ranks (without the +inf padding) on a rank whose handle was made for
+    ``m_local`` rows: dict as ``predict_exact``, ``branch`` one of ``GATHERED_BRANCHES``.  ``shift``: the bit above which the list's keys
+    agree -- 42 is what the kernel matches on, 31 the other reading of its comment; the sharded cases are built so that both give the
+    same list (tests/test_sharded_stage_cases_host.py)."""
     b = f64_bits(keys)
     s = np.sort(b)
     want = (b.size - 1) // 2
-    pre = s >> np.uint64(31)
+    pre = s >> np.uint64(shift)
     lo = int(np.searchsorted(pre, pre[want], side="left"))
     cnt = int(np.searchsorted(pre, pre[want], side="right")) - lo
-    assert cnt <= 2 * m_max
-    return dict(cnt=cnt, rank=want - lo, branch="count" if cnt <= COUNT_LIMIT else "digits", key=bits_f64(s[want]),
-                neighbours=_neighbours(s[lo:lo + cnt], want - lo))
+    cap = 2 * int(m_local)
+    if cnt <= COUNT_LIMIT:
+        branch = "count" if cnt <= cap else "overflow-short"
+    else:
+        branch = "digits" if cnt <= cap else "overflow-long"
+    return dict(cnt=cnt, rank=want - lo, branch=branch, key=bits_f64(s[want]), neighbours=_neighbours(s[lo:lo + cnt], want - lo))
+
+
+def gathered_model(abs_all, m_total, m_local, faults=()):
+    """The select of stage 2 on the gathered buffer ``abs_all`` (the ranks' slots in rank order, each padded with +inf to 2 m_pad keys) as
+    the kernels run it: the rank wanted is that of the 2 ``m_total`` real keys, the list is truncated at 2 ``m_local`` entries, an
+    overflowed list goes to the digits over the whole buffer.  Returns the median as a float (None where a broken model finds none).
+    ``faults``: ``rank_from_count_all`` (the rank taken from the buffer's length, padding included), ``truncated_list_ranked`` (a list
+    of cnt <= 1024 entries ranked by counting although only its first 2 m_local were written: the others read as zero bits)."""
+    bits = [int(x) for x in f64_bits(abs_all)]
+    count = len(bits) if "rank_from_count_all" in faults else 2 * int(m_total)
+    want = (count - 1) // 2
+    a = np.array(bits, dtype=np.uint64)
+    s = np.sort(a)
+    pre = int(s[want]) >> LIST_SHIFT
+    r = want - int((a >> np.uint64(LIST_SHIFT) < np.uint64(pre)).sum())
+    lst = [k for k in bits if k >> LIST_SHIFT == pre]
+    cap = 2 * int(m_local)
+    if len(lst) > cap:
+        if "truncated_list_ranked" in faults and len(lst) <= COUNT_LIMIT:
+            out = _rank_by_counting(lst[:cap] + [0] * (len(lst) - cap), r, ())
+            return None if out is None else bits_f64(out)
+        lst = bits                                                    # the fallback: digits over every gathered key
+    out = finish_list(lst, r, 0) if len(lst) <= cap else _radix(lst, r, pre, [(sel_shift(p), sel_width(p)) for p in (2, 3, 4, 5)])
+    return None if out is None else bits_f64(out)
 
 
 def predict_warm(keys, warm_lo, shift, list_cap, force_miss=False):
@@ -191,7 +238,7 @@ def _radix(lst, want, prefix, shifts_widths, faults=()):
 
 def finish_list(lst, want, mode, warm_base=0, shift=44, faults=()):
     """``select_finish_list`` on a list of bit patterns (Python ints, the order the kernel left them in): the key of rank ``want``, or
-    None where the (broken) model finds none.  mode 0: the keys share their top 32 bits; 1: the keys of one warm bin."""
+    None where the (broken) model finds none.  mode 0: the keys agree above bit ``LIST_SHIFT``; 1: the keys of one warm bin."""
     cnt = len(lst)
     limit = COUNT_LIMIT + 2 if "count_limit_high" in faults else COUNT_LIMIT
     if mode == 1 and "warm_base_bin" in faults:
@@ -221,8 +268,8 @@ def finish_list(lst, want, mode, warm_base=0, shift=44, faults=()):
             return (warm_base + _radix(rel, r, d, plan)) & MASK64
         except IndexError:                                            # (a rank beyond the sub-bin: nothing is found)
             return None
-    prefix = lst[0] >> 31 if lst else 0
-    return _radix(lst, want, prefix, [(sel_shift(p), sel_width(p)) for p in (3, 4, 5)])
+    prefix = lst[0] >> LIST_SHIFT if lst else 0
+    return _radix(lst, want, prefix, [(sel_shift(p), sel_width(p)) for p in (2, 3, 4, 5)])
 
 
 def select_model(slot_keys, m, m_max, warm=None, items=SEL_ITEMS, faults=()):
@@ -239,11 +286,11 @@ def select_model(slot_keys, m, m_max, warm=None, items=SEL_ITEMS, faults=()):
     a = np.array(keys, dtype=np.uint64)
     if warm is None:
         s = np.sort(a)
-        pre = int(s[min(want, s.size - 1)]) >> 31
-        lst = [k for k in keys if k >> 31 == pre]
+        pre = int(s[min(want, s.size - 1)]) >> LIST_SHIFT
+        lst = [k for k in keys if k >> LIST_SHIFT == pre]
         if "list_cap_short" in faults and len(lst) >= 2 * m_max:
             lst[2 * m_max - 1] = 0                                    # the guard `base + off < 2 m_max` one too tight: the slot is never written
-        r = want - int((a >> np.uint64(31) < np.uint64(pre)).sum())
+        r = want - int((a >> np.uint64(LIST_SHIFT) < np.uint64(pre)).sum())
         out = finish_list(lst, r, 0, faults=faults)
     else:
         lo, shift = int(warm["lo"]), int(warm["shift"])

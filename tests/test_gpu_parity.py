@@ -401,66 +401,7 @@ def test_BA_call_surface_matches_reference_signature(c1):
 
 
 # ------------------------------------------------------------------------------------------------ sharded stages
-class _EmulatedRanks:
-    """R ranks of the observation-sharded mode on ONE GPU: one engine per rank holding its row slice, the three RCCL
-    all-gathers replaced by device-side concatenation.  Drives the HIP stage entry points vba_sh_stage1..4 exactly as
-    vinsat_amd/dist.py:ShardedBA.step does."""
-
-    def __init__(self, n, m, ranks, xyz, uv, conf, ii, K, cumrot, time_idx):
-        import torch
-        from vinsat_amd.dist import HipStageEngine, shard_bounds
-        from vinsat_amd.engine import BAEngine
-        self.torch, self.n, self.m, self.ranks = torch, n, m, ranks
-        b = shard_bounds(m, ranks)
-        m_pad = -(-m // ranks)
-        self.engs = []
-        for r in range(ranks):
-            lo, hi = int(b[r]), int(b[r + 1])
-            e = BAEngine(n, hi - lo)
-            e.upload_observations(xyz[lo:hi], uv[lo:hi], conf[lo:hi], ii[lo:hi], n)
-            e.upload_window(K, cumrot, time_idx)
-            self.engs.append(HipStageEngine(e))
-        pc = self.engs[0].partial_count(n)
-        f64 = dict(dtype=torch.float64, device="cuda")
-        self.abs_l = [torch.full((2 * m_pad,), float("inf"), **f64) for _ in range(ranks)]
-        self.part_l = [torch.empty(pc, **f64) for _ in range(ranks)]
-        self.trial_l = [torch.empty(2, **f64) for _ in range(ranks)]
-
-    def set_states(self, st, lam):
-        for e in self.engs:
-            e.set_states(st, lam)
-
-    def call(self, it, init):
-        """One BA() call on every emulated rank; returns the number of stage-3 rounds (LM trials + pivoted repeats)."""
-        torch, engs = self.torch, self.engs
-        for r, e in enumerate(engs):
-            e.stage1(it, init, self.m, self.abs_l[r])
-        abs_all = torch.cat(self.abs_l)
-        for r, e in enumerate(engs):
-            e.stage2(abs_all, self.part_l[r])
-        part_all = torch.cat(self.part_l)
-        first, rounds = True, 0
-        while True:
-            for r, e in enumerate(engs):
-                e.stage3(part_all if first else None, self.ranks, self.trial_l[r])
-            trial_all = torch.cat(self.trial_l)
-            done = [e.stage4(trial_all, self.ranks) for e in engs]
-            first = False
-            rounds += 1
-            assert all(d == done[0] for d in done)
-            if done[0]:
-                return rounds
-            assert rounds < 12
-
-    def results(self):
-        outs = [e.get_states() for e in self.engs]
-        for o in outs:      # every rank holds bit-identical normal equations, so bit-identical states and damping
-            assert np.array_equal(o[0], outs[0][0]) and o[1] == outs[0][1]
-        return outs[0]
-
-    def close(self):
-        for e in self.engs:
-            e.close()
+from emulated_ranks import EmulatedRanks as _EmulatedRanks      # (imported from here by the sharded tests of other modules)
 
 
 @pytest.mark.parametrize("ranks", [2, 3])
@@ -527,10 +468,11 @@ def test_sharded_c4_window_on_eight_emulated_ranks_vs_reference_states():
 
 def test_median_with_massive_ties_and_signed_zero():
     """All residuals identical (and a block of exact zeros): the radix select must still return the exact lower
-    median.  Most keys share their top 32 bits with the median -- the offset is exactly 3.0, so the projection's rounding of either
-    sign splits them over two prefixes: the device's keys put 1063 of the 1280 in the compacted list -- which is more than is
-    ranked by counting, so digits 3 .. 5 finish the select.  (Not the overflow fallback: a list of an unsharded handle holds
-    2 m_max keys and a window has no more; tests/test_gpu_select_paths.py lists the branches nothing reaches.)"""
+    median.  Most keys agree with the median in the bits the compacted list is keyed on (``key >> 42``: sign, exponent, 10 bits of
+    the mantissa) -- the offset is exactly 3.0, a boundary of those bits as of the top 32, so the projection's rounding of either
+    sign splits the keys over two prefixes: the device's keys put 1063 of the 1280 in the list -- which is more than is ranked by
+    counting, so the digits (2 from the pass's histogram, 3 .. 5 over the list) finish the select.  (Not the overflow fallback: a list of an unsharded handle holds
+    2 m_max keys and a window has no more; tests/test_gpu_sharded_stages.py runs it on sharded handles.)"""
     from vinsat_amd.engine import BAEngine
     from vinsat_amd import od_pipe, synth
     det, orb = synth.make_sequence(synth.WindowConfig("ties", 16, 40, 5), seed=2)

@@ -34,9 +34,10 @@ Branches of ``select_finish_list`` that no accepted setting reaches (removing th
   cnt <= kWarmCount in warm mode    needs warm_shift < 8 (the sub-bin branch in front of it takes every list of <= 1024 keys otherwise);
                                     ``vba_set_warm_shift`` accepts 42 .. 51
   remaining <= 11                   the same: remaining = warm_shift >= 42
-  the overflow fallback             cnt > 2 m_max: on an unsharded handle the list holds 2 m_max keys and a window has no more
   lo == ~0 (``no-range``)           a carried median that is zero or denormal; the weights of the call that produced it are not finite,
                                     and no case was found that gets there otherwise
+The overflow fallback (cnt > 2 m_max) is not among them: the handles of this module hold all their keys, but a sharded handle selects
+among the gathered keys of all ranks with a list sized for its own slice.  tests/test_gpu_sharded_stages.py runs it, short and long.
 """
 import numpy as np
 import pytest

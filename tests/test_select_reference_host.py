@@ -39,7 +39,8 @@ def test_warm_range_and_bins_on_known_values():
 
 
 def _prefix_set(n_list, below, above):
-    """``n_list`` keys sharing the top 32 bits of 2.7 with ``below`` keys under and ``above`` keys over them."""
+    """``n_list`` keys sharing the top 32 bits of 2.7 -- hence also the bits above 42 that the compacted list is keyed on
+    (``select_reference.LIST_SHIFT``) -- with ``below`` keys under and ``above`` keys over them, none of which shares even those."""
     base = (int(S.f64_bits([2.7])[0]) >> 31) << 31
     return _f([base + 5 * i for i in range(n_list)] + [BITS_1 + i for i in range(below)] + [int(S.f64_bits([8.0])[0]) + i for i in range(above)])
 

@@ -2,7 +2,7 @@
 //
 //   k_select_pass<P>   exact select by most-significant-digit radix select: digit 0 (exponent) is histogrammed inside
 //                      k_obs_residual (vba_obs.hip), digits 1 and 2 read the keys once each, the second of them compacting
-//                      the (few) keys that match the 32 known bits, and select_finish finishes digits 3..5 on that short list
+//                      the (few) keys that match digits 0 and 1 (key >> 42), and select_finish finishes digits 3..5 on that short list
 //   k_select_warm      on carried keys: the trial that produced the keys binned them around the median of its own call
 //                      (warm_bin, vba_device.h), so ONE pass compacts the bin of the wanted rank; in a chained schedule its
 //                      prologue is the accept test of the call in front (vba_decide.h).  Batched handles; latency mode keeps

@@ -122,14 +122,16 @@ __device__ __forceinline__ int warm_front(const DevView& V, int w, bool fold_her
     return hit ? kWarmHit : kWarmMiss;
 }
 
-// Finishes the select on the compacted list (keys whose top 32 bits are known to match): returns the lower median
-// c_obs to every thread of the (256-thread) block.  It is the prologue of k_obs_accumulate -- every block of a window
-// redoes it (a handful of keys: rank by counting) instead of one more single-block kernel on the critical path; long
-// lists (massive ties) take digits 3, 4, 5 with a block-local histogram each, the full key array if the list
-// overflowed.  A list made by k_select_warm (one warm bin) is ranked by counting while short, by radix digits of the offset
-// inside the bin otherwise.
+// Finishes the select on the compacted list (the keys that k_select_pass<2, true> found to match digits 0 and 1, key >> 42;
+// digit 2 of the wanted key is known from that pass's histogram): returns the lower median c_obs to every thread of the
+// (256-thread) block.  It is the prologue of k_obs_accumulate -- every block of a window redoes it (a handful of keys:
+// rank by counting) instead of one more single-block kernel on the critical path; long lists (massive ties) take digits
+// 3, 4, 5 with a block-local histogram each, the full key array if the list overflowed -- at any length: in sharded mode
+// the list has room for this rank's rows and is filled from the gathered keys of all ranks, so a list of a few hundred
+// keys can have overflowed (tests/test_gpu_sharded_stages.py).  A list made by k_select_warm (one warm bin) is ranked by
+// counting while short, by radix digits of the offset inside the bin otherwise.
 // ck: the list (capacity `cap` entries, cnt of them valid -- cnt > cap: it overflowed), want: the rank wanted among them,
-// mode 0: keys sharing the 32-bit prefix of an exact select, 1: the keys of one warm bin starting at warm_base.
+// mode 0: keys sharing digits 0 and 1 of an exact select, 1: the keys of one warm bin starting at warm_base.
 // speculate: load the first 1024 entries before cnt is known to the caller's satisfaction (one round trip instead of two).
 __device__ __forceinline__ double select_finish_list(const DevView& V, int w, const double* ck, int64_t cap, unsigned cnt, long long want,
                                                      int mode, unsigned long long warm_base, bool speculate, unsigned* lh /*[kSelBins]*/,
@@ -211,7 +213,9 @@ __device__ __forceinline__ double select_finish_list(const DevView& V, int w, co
         __syncthreads();
         return bits_f64(skeys[1024]);
     }
-    if (cnt <= (mode ? (unsigned)kWarmCount : 1024u)) {
+    // (an exact-mode list that overflowed -- cnt > cap, sharded mode: the list is sized for this rank's rows and filled from the
+    // keys of all ranks -- holds only its first `cap` entries, however short it is: it goes to the fallback below)
+    if (cnt <= (mode ? (unsigned)kWarmCount : 1024u) && (mode != 0 || (int64_t)cnt <= cap)) {
         // the wanted key is the one of rank `want` among the list -- rank each key by counting (ties broken by position)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
