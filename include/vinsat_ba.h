@@ -642,8 +642,8 @@ int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, flo
  * (d a_i / d theta_i, then d a_i / d theta_{i+1}, row major); 9: the edges' shares sigma_att |a|^2 [n - 1] of the cost. */
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity);
 /* The orbit-dynamics factor with the velocities as unknowns, opt-in per handle, after vba_schur_upload.  time_idx [n]: the second
- * of every pose; every gap time_idx[i + 1] - time_idx[i] in 1 .. 64 (the domain of the sequential propagation; longer gaps stay
- * with the fixed-landmark path).  For every edge i -> i + 1 the reference's residual (BA_utils.py:467-476, 501-509)
+ * of every pose; every gap time_idx[i + 1] - time_idx[i] in 1 .. 64 (the domain of the sequential propagation; longer gaps are
+ * vba_schur_enable_dynamics_long's, below).  For every edge i -> i + 1 the reference's residual (BA_utils.py:467-476, 501-509)
  *   r_i = D (propagate(p_i, v_i; gap one-second RK4 steps of the J2 model) - (p_{i+1}, v_{i+1})),  D = diag(1, 1, 1, 100, 100, 100),
  * Jacobians D Phi_i at pose i and -D at pose i + 1, weight sigma_dyn, Gauss-Newton (sigma J^T J, -sigma J^T r); the cost gains
  * sigma_dyn sum |r_i|^2.  No wmax_scale: the rows keep the weights the handle holds.  The ATTITUDE factor of the fixed-landmark
@@ -658,6 +658,24 @@ int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t cap
  * Errors: VBA_EINVAL for n < 2, a gap outside 1 .. 64, a time_idx that does not increase, a sigma_dyn that is not positive and
  * finite; VBA_ESTATE before the upload or on a handle that has the factor already. */
 int vba_schur_enable_dynamics(vba_schur_handle h, const int* time_idx /*[n]*/, double sigma_dyn);
+/* vba_schur_enable_dynamics for the window of a later pass of a sequence: the same factor, contract, errors and downstream entries
+ * (vba_schur_enable_attitude and every _dyn / _att query serve such a handle as a dynamics handle), except that gaps of
+ * 65 .. VBA_MAX_GAP steps are accepted (VBA_EINVAL beyond, naming the poses).  An edge of more than 64 steps is propagated parallel
+ * in time (the parareal chain and the ordered product of sub-chunk transition matrices of the fixed-landmark path), within rounding
+ * of the serial walk up to ~1000 s and within the defect of the stop rule (~1e-13 relative) beyond; edges of 64 steps or fewer keep
+ * the kernels and the bits of vba_schur_enable_dynamics, and on a window without a long gap every output has the bits of that entry.
+ * The chain of an accepted trial is carried into the next call.  No cap on the number of long edges.  With VBA_SCHUR_LONG_SERIAL=1
+ * in the environment when this is called, the long edges take the serial lanes too (a comparison: ~10^5 dependent instructions per
+ * edge at 935 s). */
+int vba_schur_enable_dynamics_long(vba_schur_handle h, const int* time_idx /*[n]*/, double sigma_dyn);
+/* The poses i whose edge i -> i + 1 is propagated parallel in time on this handle, in index order: *count of them (none on a handle
+ * of vba_schur_enable_dynamics or under VBA_SCHUR_LONG_SERIAL=1); idx (may be null) receives them, VBA_EINVAL if cap < *count.
+ * VBA_ESTATE on a handle without the dynamics factor. */
+int vba_schur_long_edges(vba_schur_handle h, int* idx, int cap, int* count);
+/* Milliseconds (HIP events) of the cost kernels of the last trial of vba_schur_iterate: the rows, the prior and, on a handle with
+ * them, the dynamics and attitude edges at the trial state; 0 before the first trial.  Beside vba_schur_last_ms, whose three
+ * intervals end before the trial's cost. */
+int vba_schur_last_trial_cost_ms(vba_schur_handle h, float* ms);
 /* The Gauss-Newton attitude factor, opt-in per handle, after vba_schur_enable_dynamics.  cumrot [n][4]: the rotation accumulated over
  * the gap after pose i (scalar last, as vba_host_gap_rotations gives it); row n - 1 is ignored.  Rows are used as given, not
  * renormalised.  For every edge i -> i + 1, with (x) the Hamilton product:

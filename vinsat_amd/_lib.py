@@ -94,6 +94,9 @@ SIGNATURES = {
     "vba_schur_last_ms": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
     "vba_schur_debug_fetch": (c_int, [c_void_p, c_int, PD, c_int64]),
     "vba_schur_enable_dynamics": (c_int, [c_void_p, POINTER(c_int), c_double]),
+    "vba_schur_enable_dynamics_long": (c_int, [c_void_p, POINTER(c_int), c_double]),
+    "vba_schur_long_edges": (c_int, [c_void_p, POINTER(c_int), c_int, POINTER(c_int)]),
+    "vba_schur_last_trial_cost_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_enable_attitude": (c_int, [c_void_p, PD, c_double]),
     "vba_schur_covariance": (c_int, [c_void_p, c_double, PD, PD, PD, POINTER(c_int)]),
     "vba_schur_last_covariance_ms": (c_int, [c_void_p, POINTER(c_float)]),

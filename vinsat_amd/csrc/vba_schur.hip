@@ -34,6 +34,8 @@
 //   vba_schur_snoop.hip   vba_schur_snoop, _dyn, _att behind schur_snoop_call, vba_schur_rejected, vba_schur_snoop_restore and their passes
 //   vba_schur_robust.hip  vba_schur_reweight, vba_schur_get_weights, vba_schur_median and their passes
 //   vba_schur_dyn.hip     vba_schur_enable_dynamics and the kernels of the factor
+//   vba_schur_dyn_long.hip  vba_schur_enable_dynamics_long, vba_schur_long_edges and the kernels of the edges of more than 64 steps: parallel
+//                         in time (bodies shared with the fixed-landmark path: vba_long_body.h; the host's plan: vba_schur_dyn_long.h)
 //   vba_schur_att.hip     vba_schur_enable_attitude and the kernels of the Gauss-Newton attitude factor (bodies: vba_schur_att_math.h)
 //
 // Kernels (all reductions in a fixed order -- no float atomics):
@@ -75,9 +77,15 @@
 // Robust re-weighting (vba_schur_reweight, vba_schur_median: the passes of vba_schur_robust.hip)
 // Orbit-dynamics factor with velocity unknowns (vba_schur_enable_dynamics: the kernels of vba_schur_dyn.hip; the reduced system
 // becomes [6 n pose | 3 n velocity] unknowns, the build and factor kernels fill and factorise it unchanged)
+// Long gaps of that factor (vba_schur_enable_dynamics_long: behind k_sdyn_edges, for the edges of more than 64 steps only)
+//   k_sdyn_long_chain    wave per long edge: the parareal chain from the edge's start state into its pool slot, unless it is there
+//   k_sdyn_long_tangent  eight workgroups of 128 per long edge: transition matrices of 16 sub-chunks each, their ordered product
+//   k_sdyn_long_finish   wave per long edge: Phi from the partial products; A = D Phi, r, ecost at the edge's index
+//   k_sdyn_long_cost     wave per long edge: sigma |r|^2 at the states given into a partial slot of its own; the chain stays in the pool
 // Gauss-Newton attitude factor on such a handle (vba_schur_enable_attitude: the kernels of vba_schur_att.hip behind those of the orbit
 // factor, in the build and in the cost; symmetric positive semidefinite blocks on the attitude unknowns, the same Cholesky)
 #include "vba_schur_context.h"
+#include "vba_schur_dyn_long.h"
 
 namespace {
 
@@ -249,21 +257,27 @@ int schur_outputs_finish(SchurScratch& Z, hipStream_t s, int bad, const Out* out
     });
 }
 
-static int schur_cost(vba_schur_handle h, const double* states, const double* X, double* cost) {
+// trial: the states are those of a trial (the chains of the long edges go where an accepted trial's next build finds them; the chains
+// of the resident states where this call's build does)
+static int schur_cost(vba_schur_handle h, const double* states, const double* X, double* cost, bool trial) {
     SchurView V = h->V;
     SchurDyn& D = h->dyn;
     SchurAtt& T = h->att;
+    if (trial) SCHK(hipEventRecord(h->ev[0], h->stream));        // (the build's interval was read before the trial's cost began)
     hipLaunchKernelGGL(k_cost, dim3(V.npart), dim3(256), 0, h->stream, V, states, X);
     if (D.enabled) schur_dyn_cost_launch(schur_dyn_view(h, V), states, h->stream);
+    if (D.nlong > 0) schur_dyn_long_cost_launch(schur_dyn_view(h, V), states, trial ? D.par ^ 1 : D.par, h->stream);
     if (T.enabled) schur_att_cost_launch(schur_att_view(h, V), states, h->stream);
     SCHK(hipGetLastError());
+    if (trial) SCHK(hipEventRecord(h->ev[4], h->stream));
     SCHK(hipMemcpyAsync(h->h_part.data(), V.part, (size_t)V.npart * 8, hipMemcpyDeviceToHost, h->stream));
-    if (D.enabled) SCHK(hipMemcpyAsync(D.h_part.data(), D.part, (size_t)D.npart * 8, hipMemcpyDeviceToHost, h->stream));
+    if (D.enabled) SCHK(hipMemcpyAsync(D.h_part.data(), D.part, (size_t)(D.npart + D.nlong) * 8, hipMemcpyDeviceToHost, h->stream));
     if (T.enabled) SCHK(hipMemcpyAsync(T.h_part.data(), T.part, (size_t)T.npart * 8, hipMemcpyDeviceToHost, h->stream));
     SCHK(hipStreamSynchronize(h->stream));
+    if (trial) (void)hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[4]);
     double s = 0.0;
     for (int b = 0; b < V.npart; ++b) s += h->h_part[b];      // fixed order
-    if (D.enabled) for (int b = 0; b < D.npart; ++b) s += D.h_part[b];     // ... the dynamics partials after the rows' and the prior's
+    if (D.enabled) for (int b = 0; b < D.npart + D.nlong; ++b) s += D.h_part[b];   // ... the dynamics partials after the rows' and the prior's (the long edges' behind the blocks')
     if (T.enabled) for (int b = 0; b < T.npart; ++b) s += T.h_part[b];     // ... and the attitude partials after those
     *cost = s;
     return VBA_OK;
@@ -437,7 +451,7 @@ int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, dou
     SchurView V = h->V;
     V.lamda = lamda;
     V.states = h->S0; V.X = h->X0buf; V.states_new = h->S1; V.X_new = h->X1buf;
-    if (int rc = schur_cost(h, V.states, V.X, cost_before)) return rc;
+    if (int rc = schur_cost(h, V.states, V.X, cost_before, false)) return rc;
     SCHK(hipEventRecord(h->ev[0], s));
     if (int rc = schur_build_factor(h, V, s, h->d_info, h->ev[1])) return rc;
     SCHK(hipEventRecord(h->ev[2], s));
@@ -461,9 +475,9 @@ int vba_schur_iterate(vba_schur_handle h, double lamda, double* cost_before, dou
         *accepted = 0;
         return VBA_OK;
     }
-    if (int rc = schur_cost(h, V.states_new, V.X_new, cost_after)) return rc;
+    if (int rc = schur_cost(h, V.states_new, V.X_new, cost_after, true)) return rc;
     *accepted = (*cost_after < *cost_before) ? 1 : 0;
-    if (*accepted) { std::swap(h->S0, h->S1); std::swap(h->X0buf, h->X1buf); }
+    if (*accepted) { std::swap(h->S0, h->S1); std::swap(h->X0buf, h->X1buf); h->dyn.par ^= 1; }   // (the trial's chains are the next build's)
     return VBA_OK;
 }
 
@@ -478,6 +492,12 @@ int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, flo
     if (build_ms) *build_ms = h->ms[0];
     if (factor_ms) *factor_ms = h->ms[1];
     if (solve_ms) *solve_ms = h->ms[2];
+    return VBA_OK;
+}
+
+int vba_schur_last_trial_cost_ms(vba_schur_handle h, float* ms) {
+    if (!h || !ms) return sfail(VBA_EINVAL, "null argument");
+    *ms = h->ms[3];
     return VBA_OK;
 }
 

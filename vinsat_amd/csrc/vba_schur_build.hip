@@ -2,6 +2,7 @@
 // needs (Cinv, wl, E, Y) from the view's state, weights and damping.  vba_schur.hip carries the map of the units; the view and the
 // row geometry are vba_schur_context.h's.
 #include "vba_schur_context.h"
+#include "vba_schur_dyn_long.h"
 
 namespace {
 
@@ -146,6 +147,7 @@ void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, c
     if (h->dyn.enabled) {       // the dynamics blocks on top of the reprojection blocks (vba_schur_covariance_dyn brings arrays of its own)
         const SchurDynView W = dyn ? *dyn : schur_dyn_view(h, V);
         schur_dyn_edges_launch(W, V.states, s);
+        if (W.nlong > 0) schur_dyn_long_edges_launch(W, V.states, s);      // the edges k_sdyn_edges left alone
         schur_dyn_scatter_launch(W, s);
         if (h->att.enabled) {   // the attitude blocks behind them: symmetric positive semidefinite, on the attitude unknowns alone
             const SchurAttView T = att ? *att : schur_att_view(h, V);

@@ -219,8 +219,13 @@ struct SchurDyn {
     double sigma = 0.0;
     int* steps = nullptr;
     double *r = nullptr, *A = nullptr, *ecost = nullptr, *part = nullptr;
-    int npart = 0;
+    int npart = 0;              // block partials; the long edges' partials lie behind them (h_part holds both)
     std::vector<double> h_part;
+    // long edges of a handle of vba_schur_enable_dynamics_long (vba_schur_dyn_long.h): none on any other handle
+    int nlong = 0, par = 0, long_pool_states = 0;
+    int *long_idx = nullptr, *long_off = nullptr;
+    double* long_pool = nullptr;
+    std::vector<int> h_long_idx;
 };
 
 // State of vba_schur_enable_attitude: the gap rotations, the factor of the last build and the partials of its cost, and (q_*) the
@@ -334,6 +339,8 @@ void schur_pow_rows_launch(vba_schur_handle h, const SchurView& V, double ncp);
 // ---- vba_schur_dyn.hip
 // the dynamics arrays of a handle with the factor enabled, at the damping of the view
 SchurDynView schur_dyn_view(vba_schur_handle h, const SchurView& V);
+// the body of vba_schur_enable_dynamics and of vba_schur_enable_dynamics_long (long_gaps: gaps up to VBA_MAX_GAP are accepted)
+int schur_dyn_enable(vba_schur_handle h, const int* time_idx, double sigma_dyn, bool long_gaps);
 
 // ---- vba_schur_att.hip
 // the attitude arrays of a handle with that factor enabled; query: the arrays of vba_schur_covariance_dyn's build in their place

@@ -11,14 +11,22 @@ struct SchurDynView {
     int n, Npad;
     double sigma;                   // sigma_dyn
     double lamda;                   // damping of the trial (velocity diagonal)
-    const int* steps;               // [n - 1] one-second steps of edge i -> i + 1, each in 1 .. kSchurDynMaxGap (checked on the host)
+    const int* steps;               // [n - 1] one-second steps of edge i -> i + 1, each in 1 .. kSchurDynMaxGap (checked on the host); on a
+                                    // handle of vba_schur_enable_dynamics_long a long edge holds MINUS its steps (vba_schur_dyn_long.h)
     double* r;                      // [n - 1][6] residual of the last build
     double* A;                      // [n - 1][36] D Phi of the last build, row major
     double* ecost;                  // [n - 1] sigma |r_e|^2 of the last build
-    double* part;                   // [npart] block partials of the dynamics cost, one per 256 edges
+    double* part;                   // [npart + nlong] block partials of the dynamics cost, one per 256 edges, then one per long edge
     int npart;
     double* S;                      // [Npad][Npad] the reduced system (lower triangle), N = 9 n
     double* g;                      // [Npad] right-hand side, then the step: [6 n of the poses | 3 n of the velocities]
+    // long edges (vba_schur_dyn_long.hip; nlong = 0 on a handle without one: none of this is read)
+    int nlong;
+    int par;                        // parity of the pool the build reads its chains from (flips with every accepted trial)
+    const int* long_idx;            // [nlong] pose i of long edge k, in index order
+    const int* long_off;            // [nlong] offset of its slot in a pool, in states of six doubles
+    double* long_pool;              // [2][long_pool_states][6] the chains, one pool per parity
+    int long_pool_states;
 };
 
 inline int schur_dyn_partials(int n) { return (n - 1 + 255) / 256; }
@@ -29,7 +37,7 @@ void schur_dyn_edges_launch(const SchurDynView& W, const double* states, hipStre
 void schur_dyn_scatter_launch(const SchurDynView& W, hipStream_t s);
 // the velocity columns of states_new = those of states + dv (after k_lm_update, which leaves them as they were)
 void schur_dyn_update_launch(const SchurDynView& W, const double* states, double* states_new, hipStream_t s);
-// part[b] = sum over the edges of block b of sigma |r_e|^2 at `states` (residual-only propagation), fixed order
+// part[b] = sum over the edges of block b of sigma |r_e|^2 at `states` (residual-only propagation), fixed order; a long edge adds nothing
 void schur_dyn_cost_launch(const SchurDynView& W, const double* states, hipStream_t s);
 
 // The Gauss-Newton attitude factor on top of it (vba_schur_enable_attitude; kernels: vba_schur_att.hip, bodies: vba_schur_att_math.h)

@@ -19,7 +19,9 @@
 
 namespace vba {
 
-constexpr int kSchurDynMaxGap = 64;     // the domain of the sequential propagation; longer gaps are vba_long.hip's and stay out
+// the domain of the sequential propagation (k_sdyn_edges, k_sdyn_cost) and all that vba_schur_enable_dynamics accepts; longer gaps, up
+// to VBA_MAX_GAP, are vba_schur_enable_dynamics_long's: parallel in time, vba_schur_dyn_long.hip
+constexpr int kSchurDynMaxGap = 64;
 constexpr int kSchurDynItems = 78;      // work items of the scatter per pose: 36 diagonal, 36 sub-diagonal block entries, 6 of g
 
 VBA_HD double schur_dyn_d(int c) { return c < 3 ? 1.0 : kVelCoeff; }

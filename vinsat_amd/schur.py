@@ -110,10 +110,12 @@ class SchurBA:
     """Device-resident free-landmark BA problem: ``n`` poses, ``L`` landmarks, ``m`` observation rows."""
 
     def __init__(self, states, landmarks0, uv, weights, pose_of_row, landmark_of_row, intrinsics, sigma_prior=0.05, device=0,
-                 time_idx=None, sigma_dyn=None, cumrot=None, sigma_att=None):
+                 time_idx=None, sigma_dyn=None, cumrot=None, sigma_att=None, long_gaps=False):
         """``time_idx [n]`` (the second of every pose) and ``sigma_dyn`` together switch on the orbit-dynamics factor with the
         velocities as unknowns (``vba_schur_enable_dynamics`` in ``include/vinsat_ba.h``: gaps of 1 .. 64 s); with neither the
-        handle is the purely visual bundle adjustment.  ``cumrot [n,4]`` (the rotation accumulated over the gap after every pose,
+        handle is the purely visual bundle adjustment.  ``long_gaps=True`` (with both) switches it on through
+        ``vba_schur_enable_dynamics_long`` instead: gaps up to ``VBA_MAX_GAP`` seconds, the window of a later pass of a sequence;
+        edges of more than 64 s are propagated parallel in time (:meth:`long_edges` names them), everything else is as it was.  ``cumrot [n,4]`` (the rotation accumulated over the gap after every pose,
         scalar last, as ``od_pipe.gap_rotations`` gives it; the last row is ignored) and ``sigma_att`` together add the
         Gauss-Newton attitude factor on such a handle (``vba_schur_enable_attitude``); ``sigma_att = sigma_dyn * QUAT_COEFF / 2``
         weights the attitude as the reference does near the solution."""
@@ -121,6 +123,8 @@ class SchurBA:
             raise ValueError("time_idx and sigma_dyn switch on the dynamics factor together: give both or neither")
         if (cumrot is None) != (sigma_att is None):
             raise ValueError("cumrot and sigma_att switch on the attitude factor together: give both or neither")
+        if long_gaps and time_idx is None:
+            raise ValueError("long_gaps is an option of the dynamics factor: give time_idx and sigma_dyn with it")
         if cumrot is not None and time_idx is None:
             raise ValueError("the attitude factor (cumrot, sigma_att) is only valid together with time_idx and sigma_dyn")
         self.lib = _lib.load()
@@ -148,7 +152,8 @@ class SchurBA:
             try:
                 if t.size != self.n:
                     raise ValueError("time_idx needs one entry per pose")
-                self._check(self.lib.vba_schur_enable_dynamics(self.h, t.ctypes.data_as(ctypes.POINTER(c_int)), float(sigma_dyn)))
+                enable = self.lib.vba_schur_enable_dynamics_long if long_gaps else self.lib.vba_schur_enable_dynamics
+                self._check(enable(self.h, t.ctypes.data_as(ctypes.POINTER(c_int)), float(sigma_dyn)))
             except Exception:
                 self.close()
                 raise
@@ -207,6 +212,12 @@ class SchurBA:
         self._check(self.lib.vba_schur_last_ms(self.h, byref(a), byref(b), byref(c)))
         return dict(build=a.value, factor=b.value, solve=c.value)
 
+    def last_trial_cost_ms(self):
+        """Milliseconds of the cost kernels of the last trial (``vba_schur_last_trial_cost_ms``), beside :meth:`last_ms`."""
+        v = c_float()
+        self._check(self.lib.vba_schur_last_trial_cost_ms(self.h, byref(v)))
+        return v.value
+
     def last_step(self):
         """``(dc [n,6], dl [L,3])`` of the last iterate."""
         out = np.empty(6 * self.n + 3 * self.L)
@@ -233,6 +244,16 @@ class SchurBA:
     def dynamics_edge_cost(self):
         """``sigma_dyn |r|^2 [n-1]``: the edges' shares of the cost at the state the last iterate started from."""
         return self._dynamics_fetch(6, (self.n - 1,))
+
+    def long_edges(self):
+        """The poses ``i`` whose edge ``i -> i + 1`` is propagated parallel in time (``vba_schur_long_edges``): the gaps of more than
+        64 s of a handle built with ``long_gaps=True``; empty on any other handle with the dynamics factor."""
+        cnt = c_int()
+        self._check(self.lib.vba_schur_long_edges(self.h, None, 0, byref(cnt)))
+        idx = np.zeros(cnt.value, dtype=np.int32)
+        if cnt.value:
+            self._check(self.lib.vba_schur_long_edges(self.h, idx.ctypes.data_as(ctypes.POINTER(c_int)), cnt.value, byref(cnt)))
+        return idx
 
     def attitude_residual(self):
         """``a [n-1,3]`` of the edges at the state the last iterate started from (a handle with the attitude factor)."""
