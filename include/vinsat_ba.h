@@ -639,7 +639,9 @@ int vba_schur_last_ms(vba_schur_handle h, float* build_ms, float* factor_ms, flo
  * last iterate; 4: the residuals r [n - 1, 6] and 5: the Jacobians D Phi [n - 1, 6, 6] of the edges at the state the last iterate
  * started from; 6: the edges' shares sigma_dyn |r|^2 [n - 1] of the cost there.  On a handle with the attitude factor (VBA_ESTATE
  * without it), all at the state the last iterate started from, 7: the residuals a [n - 1, 3]; 8: the Jacobian pairs [n - 1, 2, 3, 3]
- * (d a_i / d theta_i, then d a_i / d theta_{i+1}, row major); 9: the edges' shares sigma_att |a|^2 [n - 1] of the cost. */
+ * (d a_i / d theta_i, then d a_i / d theta_{i+1}, row major); 9: the edges' shares sigma_att |a|^2 [n - 1] of the cost.  On a handle
+ * with the state prior (VBA_ESTATE without it), all at the state the last iterate started from, 10: the residuals e [count, 9];
+ * 11: the Jacobians J [count, 3, 3]; 12: the priors' shares e^T Lambda e [count] of the cost. */
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity);
 /* The orbit-dynamics factor with the velocities as unknowns, opt-in per handle, after vba_schur_upload.  time_idx [n]: the second
  * of every pose; every gap time_idx[i + 1] - time_idx[i] in 1 .. 64 (the domain of the sequential propagation; longer gaps are
@@ -696,6 +698,44 @@ int vba_schur_last_trial_cost_ms(vba_schur_handle h, float* ms);
  * whose norm is further than 1e-6 from 1; VBA_ESTATE before the upload, on a handle without the dynamics factor, or on a handle that
  * has the attitude factor already. */
 int vba_schur_enable_attitude(vba_schur_handle h, const double* cumrot /*[n][4]*/, double sigma_att);
+/* A Gaussian prior on the 9-DoF state of chosen poses, opt-in per handle, on a handle with the dynamics factor (either enable entry;
+ * the attitude factor may be on or off, enabled before or after).  Coordinates are those of state_cov (vba_schur_covariance_dyn):
+ * x = [dp (km), dtheta, dv (km/s)], unknown u(i, c) as documented there.  For prior k on pose i = pose_idx[k], anchor [k] =
+ * (pbar [3], qbar [4] scalar last, vbar [3]) and info[k] = Lambda (9x9, symmetric, row major), with (x) the Hamilton product:
+ *   [eps, d] = conj(qbar) (x) q_i,   s = d >= 0 ? +1 : -1,   e = [p_i - pbar, 2 s eps, v_i - vbar],
+ *   F = blockdiag(I, J, I),   J = d (2 s eps) / d theta_i = s (d I + [eps]x)
+ * along the mode's retraction q <- normalise(q (x) qexp(dtheta)), so J = I at q_i = +-qbar.  Gauss-Newton: F^T Lambda F into the
+ * entries (u(i, a), u(i, b)) of the reduced system (the lower triangles of the 6x6 pose block and of the 3x3 velocity block, the whole
+ * 3x6 velocity-pose block), -F^T Lambda e into the right-hand side; the cost gains sum e^T Lambda e, at the resident and at the
+ * trial state.  Factorisation, substitutions and updates are unchanged.  A singular Lambda (position only, say) is accepted; an
+ * indefinite one shows as a non-positive pivot (vba_schur_last_info) like any other.  vba_schur_covariance_dyn includes the factor;
+ * vba_schur_reliability_dyn / _att, vba_schur_snoop_dyn / _att and vba_schur_outlier_power_dyn / _att return VBA_ESTATE on such a
+ * handle (their redundancy counts do not know the prior's equations); vba_schur_reweight, vba_schur_get_weights and vba_schur_median
+ * work unchanged.  A handle that never calls this launches what it launched before and returns the same bits.
+ * Errors: VBA_ESTATE before the upload, without the dynamics factor, or with the prior enabled already; VBA_EINVAL (the message
+ * names the entry) for a null pointer, count outside 1 .. n, an index outside 0 .. n - 1 or given twice, an anchor that is not finite
+ * or whose quaternion norm is further than 1e-6 from 1, an info block that is not finite, not symmetric to 1e-12 of its largest
+ * entry, or has a negative diagonal entry.  The handle stays usable after a refusal. */
+int vba_schur_enable_state_prior(vba_schur_handle h, int count, const int* pose_idx /*[count]*/, const double* anchor /*[count][10]*/,
+                                 const double* info /*[count][9][9]*/);
+/* The hand-off of a solved window into the prior of the next one, on a handle with the dynamics factor, at its resident state: the
+ * marginal Sigma = state_cov[n - 1] of vba_schur_covariance_dyn(h, lamda, ...) (its device part; nothing of the handle changes),
+ * propagated over `steps` one-second RK4 steps of the J2 model on the device:
+ *   (phat, vhat), Phi = the propagation of (p, v) of pose n - 1 with its transition matrix (the lanes of the dynamics factor up to 64
+ *                       steps, its parallel-in-time bodies beyond),
+ *   G      = Phi on the [dp, dv] components, R on dtheta: the matrix of dtheta' = conj(c) dtheta c, c = cumrot_gap (the rotation
+ *            accumulated over the gap, scalar last), since q (x) qexp(d) (x) c = (q (x) c) (x) qexp(conj(c) d c),
+ *   Sigma' = G Sigma G^T + steps diag(process_noise[0] x3, process_noise[1] x3, process_noise[2] x3)   (variances per second; NULL = 0),
+ *   info_out = Sigma'^-1 by a 9x9 Cholesky, one triangle computed and mirrored;  anchor_out = [phat, normalise(q (x) c), vhat]:
+ * what vba_schur_enable_state_prior takes for pose 0 of the next window.  *info: 0; 1 + the row of a non-positive pivot of the
+ * query's factorisation; -1 if Sigma' is not positive definite; when it is not 0 the outputs are NaN and the call returns VBA_OK.
+ * VBA_EINVAL: a null pointer (process_noise may be NULL), lamda negative or NaN, steps outside 1 .. VBA_MAX_GAP, a cumrot_gap that is
+ * not a unit quaternion (finite, norm within 1e-6 of 1), negative or non-finite noise; VBA_ESTATE: before the upload or before a
+ * state is set, or a handle without the dynamics factor. */
+int vba_schur_handoff(vba_schur_handle h, double lamda, int steps, const double* cumrot_gap /*[4]*/, const double* process_noise /*[3] or NULL*/,
+                      double* anchor_out /*[10]*/, double* info_out /*[9][9]*/, int* info);
+/* HIP-event time of the last vba_schur_handoff on this handle (the device part of vba_schur_covariance_dyn and the hand-off kernel) */
+int vba_schur_last_handoff_ms(vba_schur_handle h, float* ms);
 /* Covariances of the free-landmark system at the resident state: blocks of the inverse of H = [[B, E], [E^T, C]] as
  * vba_schur_iterate(h, lamda, ...) would build it there (lamda on every diagonal entry of B and C; lamda = 0, the usual
  * case, gives the undamped covariance -- the catalogue prior fixes the gauge).  With S = B - E C^-1 E^T and Y_k = E_k C_l^-1:

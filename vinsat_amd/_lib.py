@@ -98,6 +98,9 @@ SIGNATURES = {
     "vba_schur_long_edges": (c_int, [c_void_p, POINTER(c_int), c_int, POINTER(c_int)]),
     "vba_schur_last_trial_cost_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_enable_attitude": (c_int, [c_void_p, PD, c_double]),
+    "vba_schur_enable_state_prior": (c_int, [c_void_p, c_int, POINTER(c_int), PD, PD]),
+    "vba_schur_handoff": (c_int, [c_void_p, c_double, c_int, PD, PD, PD, PD, POINTER(c_int)]),
+    "vba_schur_last_handoff_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_covariance": (c_int, [c_void_p, c_double, PD, PD, PD, POINTER(c_int)]),
     "vba_schur_last_covariance_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "vba_schur_covariance_dyn": (c_int, [c_void_p, c_double, PD, PD, PD, PD, POINTER(c_int)]),

@@ -37,6 +37,8 @@
 //   vba_schur_dyn_long.hip  vba_schur_enable_dynamics_long, vba_schur_long_edges and the kernels of the edges of more than 64 steps: parallel
 //                         in time (bodies shared with the fixed-landmark path: vba_long_body.h; the host's plan: vba_schur_dyn_long.h)
 //   vba_schur_att.hip     vba_schur_enable_attitude and the kernels of the Gauss-Newton attitude factor (bodies: vba_schur_att_math.h)
+//   vba_schur_prior.hip   vba_schur_enable_state_prior and the kernels of the state prior factor; vba_schur_handoff and its kernel: the last
+//                         pose's marginal across a gap into the prior of the next window (bodies: vba_schur_prior_math.h)
 //
 // Kernels (all reductions in a fixed order -- no float atomics):
 //   k_lm_blocks     thread per landmark: C_l, w_l over its rows, C_l^-1, then E_k and Y_k = E_k C_l^-1 per row
@@ -84,6 +86,14 @@
 //   k_sdyn_long_cost     wave per long edge: sigma |r|^2 at the states given into a partial slot of its own; the chain stays in the pool
 // Gauss-Newton attitude factor on such a handle (vba_schur_enable_attitude: the kernels of vba_schur_att.hip behind those of the orbit
 // factor, in the build and in the cost; symmetric positive semidefinite blocks on the attitude unknowns, the same Cholesky)
+// State prior factor on a dynamics handle (vba_schur_enable_state_prior: the kernels of vba_schur_prior.hip behind those of the other
+// factors, in the build and in the cost; symmetric blocks on the 9x9 state blocks of the chosen poses, the same Cholesky)
+//   k_sprior_terms    thread per prior: e, J, Lambda F, Lambda e and the cost share
+//   k_sprior_scatter  block per prior, thread per target entry (45 of S, 9 of g): one owner per entry
+//   k_sprior_cost     thread per prior: e^T Lambda e at the given states, block partials
+// Window hand-off (vba_schur_handoff: the device part of vba_schur_covariance_dyn, then)
+//   k_shandoff        one workgroup: (p, v) of the last pose over the gap with Phi (the six-tangent lanes up to 64 steps, the bodies of
+//                     vba_long_body.h beyond), G Sigma G^T + noise, its inverse by a 9x9 Cholesky, the anchor
 #include "vba_schur_context.h"
 #include "vba_schur_dyn_long.h"
 
@@ -231,6 +241,12 @@ int schur_kind_check(SchurKind kind, vba_schur_handle h, const char* entry) {
     if (!h->dyn.enabled) return sfail(VBA_ESTATE, "the dynamics factor is not enabled on this handle");
     if (kind == kSchurAtt && !h->att.enabled) return sfail(VBA_ESTATE, "the attitude factor is not enabled on this handle");
     if (kind == kSchurDyn && h->att.enabled && entry) return sfail(VBA_ESTATE, std::string(entry) + kAttRefusal);
+    // (behind the checks above: their messages and their order are pinned)
+    if (entry && h->prior.enabled) {
+        std::string name(entry);
+        if (kind == kSchurAtt) name.replace(name.size() - 3, 3, "att");    // (an _att entry passes the name of its _dyn counterpart)
+        return sfail(VBA_ESTATE, name + kPriorRefusal);
+    }
     return VBA_OK;
 }
 
@@ -263,22 +279,26 @@ static int schur_cost(vba_schur_handle h, const double* states, const double* X,
     SchurView V = h->V;
     SchurDyn& D = h->dyn;
     SchurAtt& T = h->att;
+    SchurPrior& P = h->prior;
     if (trial) SCHK(hipEventRecord(h->ev[0], h->stream));        // (the build's interval was read before the trial's cost began)
     hipLaunchKernelGGL(k_cost, dim3(V.npart), dim3(256), 0, h->stream, V, states, X);
     if (D.enabled) schur_dyn_cost_launch(schur_dyn_view(h, V), states, h->stream);
     if (D.nlong > 0) schur_dyn_long_cost_launch(schur_dyn_view(h, V), states, trial ? D.par ^ 1 : D.par, h->stream);
     if (T.enabled) schur_att_cost_launch(schur_att_view(h, V), states, h->stream);
+    if (P.enabled) schur_prior_cost_launch(schur_prior_view(h, V), states, h->stream);
     SCHK(hipGetLastError());
     if (trial) SCHK(hipEventRecord(h->ev[4], h->stream));
     SCHK(hipMemcpyAsync(h->h_part.data(), V.part, (size_t)V.npart * 8, hipMemcpyDeviceToHost, h->stream));
     if (D.enabled) SCHK(hipMemcpyAsync(D.h_part.data(), D.part, (size_t)(D.npart + D.nlong) * 8, hipMemcpyDeviceToHost, h->stream));
     if (T.enabled) SCHK(hipMemcpyAsync(T.h_part.data(), T.part, (size_t)T.npart * 8, hipMemcpyDeviceToHost, h->stream));
+    if (P.enabled) SCHK(hipMemcpyAsync(P.h_part.data(), P.part, (size_t)P.npart * 8, hipMemcpyDeviceToHost, h->stream));
     SCHK(hipStreamSynchronize(h->stream));
     if (trial) (void)hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[4]);
     double s = 0.0;
     for (int b = 0; b < V.npart; ++b) s += h->h_part[b];      // fixed order
     if (D.enabled) for (int b = 0; b < D.npart + D.nlong; ++b) s += D.h_part[b];   // ... the dynamics partials after the rows' and the prior's (the long edges' behind the blocks')
     if (T.enabled) for (int b = 0; b < T.npart; ++b) s += T.h_part[b];     // ... and the attitude partials after those
+    if (P.enabled) for (int b = 0; b < P.npart; ++b) s += P.h_part[b];     // ... and the state prior's last
     *cost = s;
     return VBA_OK;
 }
@@ -286,13 +306,13 @@ static int schur_cost(vba_schur_handle h, const double* states, const double* X,
 // Build the reduced camera system of the view's state and damping and factorise it, on stream s (the bulk of a panel's trailing
 // update beside it on h->aux): S, g, Cinv, wl, E, Y, invL and *d_info are the view's and the caller's, so vba_schur_iterate runs it
 // on the handle's arrays and vba_schur_covariance on scratch of its own.  ev_built (if given) is recorded between the two parts;
-// dyn and att (if given) stand for the handle's dynamics and attitude arrays in the build.
+// dyn, att and prior (if given) stand for the handle's dynamics, attitude and state prior arrays in the build.
 int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn,
-                       const SchurAttView* att) {
+                       const SchurAttView* att, const SchurPriorView* prior) {
     SCHK(hipMemsetAsync(V.S, 0, (size_t)V.Npad * V.Npad * 8, s));
     SCHK(hipMemsetAsync(V.g, 0, (size_t)V.Npad * 8, s));
     SCHK(hipMemsetAsync(d_info, 0, 4, s));
-    schur_build_launch(h, V, s, dyn, att);
+    schur_build_launch(h, V, s, dyn, att, prior);
     if (ev_built) SCHK(hipEventRecord(ev_built, s));
     return schur_factor_launch(h, V, s, d_info);
 }
@@ -367,7 +387,8 @@ int vba_schur_destroy(vba_schur_handle h) {
     for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
     if (h->dyn.arena) hipFree(h->dyn.arena);
     if (h->att.arena) hipFree(h->att.arena);
-    for (SchurScratch* z : {&h->robust.sc, &h->snoop.sc, &h->pow.sc, &h->rel.sc, &h->q.sc}) schur_scratch_release(*z);
+    if (h->prior.arena) hipFree(h->prior.arena);
+    for (SchurScratch* z : {&h->handoff.sc, &h->robust.sc, &h->snoop.sc, &h->pow.sc, &h->rel.sc, &h->q.sc}) schur_scratch_release(*z);
     if (h->arena) hipFree(h->arena);
     delete h;
     return VBA_OK;
@@ -505,7 +526,8 @@ int vba_schur_last_trial_cost_ms(vba_schur_handle h, float* ms) {
 // [N][N] row-major matrix (upper part zero; N = 6 n, or 9 n with the dynamics factor), 2 = the 2 m keys |r| of the last
 // re-weighting; with the dynamics factor 3 = dv [n][3] of the last iteration, 4 = r [n - 1][6], 5 = D Phi [n - 1][6][6] and
 // 6 = sigma_dyn |r_e|^2 [n - 1] of its build; with the attitude factor 7 = a [n - 1][3], 8 = the Jacobian pairs [n - 1][2][3][3] and
-// 9 = sigma_att |a_e|^2 [n - 1] of its build
+// 9 = sigma_att |a_e|^2 [n - 1] of its build; with the state prior 10 = e [count][9], 11 = J [count][3][3] and 12 = e^T Lambda e [count]
+// of its build
 int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t capacity) {
     if (!h || !out) return sfail(VBA_EINVAL, "null argument");
     SCHK(hipSetDevice(h->device));
@@ -536,6 +558,15 @@ int vba_schur_debug_fetch(vba_schur_handle h, int what, double* out, int64_t cap
         const int64_t count[3] = {3 * ne, 18 * ne, ne};
         if (capacity < count[what - 7]) return sfail(VBA_EINVAL, "buffer too small");
         SCHK(hipMemcpy(out, src[what - 7], (size_t)count[what - 7] * 8, hipMemcpyDeviceToHost));
+        return VBA_OK;
+    }
+    if (what >= 10 && what <= 12) {
+        const SchurPrior& P = h->prior;
+        if (!P.enabled) return sfail(VBA_ESTATE, "the state prior is not enabled on this handle");
+        const double* src[3] = {P.e, P.J, P.share};
+        const int64_t count[3] = {9 * (int64_t)P.count, 9 * (int64_t)P.count, P.count};
+        if (capacity < count[what - 10]) return sfail(VBA_EINVAL, "buffer too small");
+        SCHK(hipMemcpy(out, src[what - 10], (size_t)count[what - 10] * 8, hipMemcpyDeviceToHost));
         return VBA_OK;
     }
     if (what == 1) {

@@ -140,7 +140,8 @@ __global__ void k_pad_identity(SchurView V) {
 
 }  // namespace
 
-void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn, const SchurAttView* att) {
+void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn, const SchurAttView* att,
+                        const SchurPriorView* prior) {
     hipLaunchKernelGGL(k_lm_blocks, dim3((V.L + 255) / 256), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pose_blocks, dim3((V.n + 15) / 16), dim3(256), 0, s, V);
     hipLaunchKernelGGL(k_pair_blocks, dim3(V.nblk), dim3(64), 0, s, V);
@@ -153,6 +154,11 @@ void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, c
             const SchurAttView T = att ? *att : schur_att_view(h, V);
             schur_att_edges_launch(T, V.states, s);
             schur_att_scatter_launch(T, s);
+        }
+        if (h->prior.enabled) { // the state prior's blocks behind both: symmetric, on the 9x9 blocks of the chosen poses alone
+            const SchurPriorView P = prior ? *prior : schur_prior_view(h, V);
+            schur_prior_terms_launch(P, V.states, s);
+            schur_prior_scatter_launch(P, s);
         }
     }
     if (V.Npad > V.N) hipLaunchKernelGGL(k_pad_identity, dim3((V.Npad - V.N + 63) / 64), dim3(64), 0, s, V);

@@ -240,6 +240,26 @@ struct SchurAtt {
     std::vector<double> h_part;
 };
 
+// State of vba_schur_enable_state_prior: the priors as uploaded, the terms of the last build and the partials of the cost, and (q_*)
+// the arrays vba_schur_covariance_dyn builds into, so that e, J and the shares stay those of the last iterate.  One allocation.
+struct SchurPrior {
+    char* arena = nullptr;
+    bool enabled = false;
+    int count = 0, npart = 0;
+    int* idx = nullptr;
+    double *anchor = nullptr, *info = nullptr;
+    double *e = nullptr, *J = nullptr, *LF = nullptr, *Le = nullptr, *share = nullptr, *part = nullptr;
+    double *q_e = nullptr, *q_J = nullptr, *q_LF = nullptr, *q_Le = nullptr, *q_share = nullptr;
+    std::vector<double> h_part;
+};
+
+// Scratch of vba_schur_handoff, allocated by the first hand-off of a handle: the chain slot of a long gap (vba_long_body.h), the
+// outputs on the device, two timing events.
+struct SchurHandoff {
+    SchurScratch sc;
+    double *pool = nullptr, *out = nullptr;
+};
+
 // why vba_schur_reliability_dyn, vba_schur_snoop_dyn and vba_schur_outlier_power_dyn refuse a handle with the attitude factor
 // (vba_schur_reliability_att, vba_schur_snoop_att and vba_schur_outlier_power_att are the queries of such a handle)
 constexpr char kAttRefusal[] = " is not available on a handle with the attitude factor: its redundancy counts and edge leverages do not "
@@ -248,6 +268,11 @@ constexpr char kAttRefusal[] = " is not available on a handle with the attitude 
 // why the plain-named queries refuse a handle with the dynamics factor (vba_schur_covariance_dyn is the covariance query of such a handle)
 constexpr char kDynRefusal[] = " is not available on a handle with the dynamics factor: its redundancy counts and gathers assume the "
                                "6 n reduced system of the reprojection rows";
+
+// why the six _dyn / _att reliability, snoop and outlier power entries refuse a handle with the state prior (vba_schur_covariance_dyn
+// serves it)
+constexpr char kPriorRefusal[] = " is not available on a handle with the state prior: its redundancy counts do not know the 9 equations "
+                                 "of every prior";
 
 // which handle an entry serves: the plain one, one with the dynamics factor, one with the attitude factor too
 enum SchurKind { kSchurPlain = 0, kSchurDyn = 1, kSchurAtt = 2 };
@@ -278,6 +303,8 @@ struct vba_schur_context {
     SchurRobust robust;         // vba_schur_reweight's state (nothing until the first re-weighting)
     SchurDyn dyn;               // vba_schur_enable_dynamics' state (nothing on a handle without the dynamics factor)
     SchurAtt att;               // vba_schur_enable_attitude's state (nothing on a handle without the attitude factor)
+    SchurPrior prior;           // vba_schur_enable_state_prior's state (nothing on a handle without the state prior)
+    SchurHandoff handoff;       // vba_schur_handoff's scratch (nothing until the first hand-off)
     int bw = 1 << 30;           // tile bandwidth of the reduced system (max |I - J| over its non-zero tiles), from the block list
 };
 
@@ -285,8 +312,10 @@ struct vba_schur_context {
 // S, g, Cinv, wl, E, Y of the view's state and damping on stream s (S and g zeroed by the caller): the reprojection blocks, the
 // dynamics blocks on a handle with the factor (the attitude blocks behind them on a handle with that factor too), the identity of the
 // padding rows.  dyn (if given) replaces the handle's own dynamics arrays: the covariance query of such a handle builds r, A, ecost in
-// its scratch and leaves the handle's as the last iterate wrote them; att (if given) does the same for the attitude arrays
-void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn = nullptr, const SchurAttView* att = nullptr);
+// its scratch and leaves the handle's as the last iterate wrote them; att (if given) does the same for the attitude arrays, prior
+// (if given) for those of the state prior, whose blocks go behind every other factor's
+void schur_build_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, const SchurDynView* dyn = nullptr, const SchurAttView* att = nullptr,
+                        const SchurPriorView* prior = nullptr);
 
 // ---- vba_schur_factor.hip
 // S = Lg Lg^T in place and the inverse diagonal factors, on stream s (the bulk of a panel's trailing update beside it on h->aux);
@@ -295,7 +324,7 @@ int schur_factor_launch(vba_schur_handle h, const SchurView& V, hipStream_t s, i
 
 // ---- vba_schur.hip
 int schur_build_factor(vba_schur_handle h, const SchurView& V, hipStream_t s, int* d_info, hipEvent_t ev_built, const SchurDynView* dyn = nullptr,
-                       const SchurAttView* att = nullptr);
+                       const SchurAttView* att = nullptr, const SchurPriorView* prior = nullptr);
 
 // -- the scaffold of the query entries (covariance, reliability, snoop, outlier power)
 // VBA_OK, or why an entry of this kind does not serve this handle: the one place that decides it.  `entry` goes in front of the
@@ -345,4 +374,8 @@ int schur_dyn_enable(vba_schur_handle h, const int* time_idx, double sigma_dyn, 
 // ---- vba_schur_att.hip
 // the attitude arrays of a handle with that factor enabled; query: the arrays of vba_schur_covariance_dyn's build in their place
 SchurAttView schur_att_view(vba_schur_handle h, const SchurView& V, bool query = false);
+
+// ---- vba_schur_prior.hip
+// the arrays of the state prior of a handle with it enabled; query: the arrays of vba_schur_covariance_dyn's build in their place
+SchurPriorView schur_prior_view(vba_schur_handle h, const SchurView& V, bool query = false);
 #pragma GCC visibility pop

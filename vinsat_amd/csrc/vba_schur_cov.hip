@@ -298,7 +298,7 @@ static SchurView query_view(vba_schur_handle h, double lamda) {
 // the info word to the host (*bad), and unless the factorisation failed the selected inverse, the gathered blocks (Q.pair, Q.pose)
 // and, with with_lm, the landmark marginals (Q.lm).  On a handle with the dynamics factor (the entries check the kind first, so the
 // handle decides): the dynamics blocks of the build go through arrays of the scratch (DW; TW likewise on a handle with the attitude
-// factor, so debug_fetch 7 .. 9 stay the last iterate's), W is needed in full (h->bw = nb - 1: nothing skipped), the product forms the
+// factor, so debug_fetch 7 .. 9 stay the last iterate's; PW on a handle with the state prior, for 10 .. 12), W is needed in full (h->bw = nb - 1: nothing skipped), the product forms the
 // listed tiles of S9^-1 only (every tile with VBA_SCHUR_COV_FULL=1), the 9x9 blocks are gathered (Q.state, Q.edge), and k_cov_gather /
 // k_lm_cov run as they are: they index by V.Npad and read the top-left 6 n x 6 n only (E9 has no velocity rows, so the landmark
 // formula stands).  The reliability query reads what this leaves resident: Q.state, Q.edge, Q.pair, Q.lm, Q.dyn_A, Q.dyn_ecost.  The
@@ -315,8 +315,11 @@ int schur_query_device(vba_schur_handle h, double lamda, bool with_lm, hipEvent_
         DW.r = Q.dyn_r; DW.A = Q.dyn_A; DW.ecost = Q.dyn_ecost; DW.part = Q.dyn_part;
     }
     if (att) TW = schur_att_view(h, V, true);
+    const bool prior = dyn && h->prior.enabled;
+    SchurPriorView PW{};
+    if (prior) PW = schur_prior_view(h, V, true);
     SCHK(hipEventRecord(ev_begin, s));
-    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr, dyn ? &DW : nullptr, att ? &TW : nullptr)) return rc;
+    if (int rc = schur_build_factor(h, V, s, Q.info, nullptr, dyn ? &DW : nullptr, att ? &TW : nullptr, prior ? &PW : nullptr)) return rc;
     SCHK(hipGetLastError());
     *bad = 0;
     SCHK(hipMemcpyAsync(bad, Q.info, 4, hipMemcpyDeviceToHost, s));

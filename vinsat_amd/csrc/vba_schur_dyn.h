@@ -61,4 +61,29 @@ void schur_att_scatter_launch(const SchurAttView& W, hipStream_t s);
 // part[b] = sum over the edges of block b of sigma |a_e|^2 at `states`, fixed order
 void schur_att_cost_launch(const SchurAttView& W, const double* states, hipStream_t s);
 
+// The state prior factor on a handle with the dynamics factor (vba_schur_enable_state_prior; kernels: vba_schur_prior.hip, bodies:
+// vba_schur_prior_math.h)
+struct SchurPriorView {
+    int n, Npad, count;
+    const int* idx;                 // [count] pose of prior k: in 0 .. n - 1, no pose twice (checked on the host)
+    const double* anchor;           // [count][10]
+    const double* info;             // [count][81] Lambda, row major
+    double* e;                      // [count][9] residual of the last build
+    double* J;                      // [count][9] d (2 s eps) / d theta of the last build, row major
+    double* LF;                     // [count][81] Lambda F of the last build
+    double* Le;                     // [count][9] Lambda e of the last build
+    double* share;                  // [count] e^T Lambda e of the last build
+    double* part;                   // [npart] block partials of the prior's cost, one per 256 priors
+    int npart;
+    double* S;                      // the reduced system and its right-hand side, as in SchurDynView
+    double* g;
+};
+
+// e, J, Lambda F, Lambda e, share at `states` [n][10]: thread per prior
+void schur_prior_terms_launch(const SchurPriorView& W, const double* states, hipStream_t s);
+// the factor's blocks into S and g, after the scatters of the other factors on the same stream; no atomics, one owner per entry
+void schur_prior_scatter_launch(const SchurPriorView& W, hipStream_t s);
+// part[b] = sum over the priors of block b of e^T Lambda e at `states`, fixed order
+void schur_prior_cost_launch(const SchurPriorView& W, const double* states, hipStream_t s);
+
 }  // namespace vba

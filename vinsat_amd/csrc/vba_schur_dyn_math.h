@@ -39,6 +39,15 @@ VBA_HD void schur_dyn_edge_column(const double* st, int steps, int c, double* xh
     for (int r = 0; r < 6; ++r) { xhat[r] = x[r]; col[r] = r < 3 ? t[r] : t[r] * kVelCoeff; }
 }
 
+// the same lane without D: col [6] = column c of Phi itself (vba_schur_handoff propagates a covariance with it)
+VBA_HD void schur_dyn_phi_column(const double* st, int steps, int c, double* xhat, double* col) {
+    double x[6] = {st[0], st[1], st[2], st[7], st[8], st[9]};
+    double t[6] = {0, 0, 0, 0, 0, 0};
+    t[c] = 1.0;
+    propagate_gap<true>(x, t, steps, 0);
+    for (int r = 0; r < 6; ++r) { xhat[r] = x[r]; col[r] = t[r]; }
+}
+
 // the prediction alone (the cost of a trial state)
 VBA_HD void schur_dyn_predict(const double* st, int steps, double* xhat) {
     double x[6] = {st[0], st[1], st[2], st[7], st[8], st[9]};

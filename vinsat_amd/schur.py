@@ -110,7 +110,7 @@ class SchurBA:
     """Device-resident free-landmark BA problem: ``n`` poses, ``L`` landmarks, ``m`` observation rows."""
 
     def __init__(self, states, landmarks0, uv, weights, pose_of_row, landmark_of_row, intrinsics, sigma_prior=0.05, device=0,
-                 time_idx=None, sigma_dyn=None, cumrot=None, sigma_att=None, long_gaps=False):
+                 time_idx=None, sigma_dyn=None, cumrot=None, sigma_att=None, long_gaps=False, state_prior=None):
         """``time_idx [n]`` (the second of every pose) and ``sigma_dyn`` together switch on the orbit-dynamics factor with the
         velocities as unknowns (``vba_schur_enable_dynamics`` in ``include/vinsat_ba.h``: gaps of 1 .. 64 s); with neither the
         handle is the purely visual bundle adjustment.  ``long_gaps=True`` (with both) switches it on through
@@ -118,7 +118,12 @@ class SchurBA:
         edges of more than 64 s are propagated parallel in time (:meth:`long_edges` names them), everything else is as it was.  ``cumrot [n,4]`` (the rotation accumulated over the gap after every pose,
         scalar last, as ``od_pipe.gap_rotations`` gives it; the last row is ignored) and ``sigma_att`` together add the
         Gauss-Newton attitude factor on such a handle (``vba_schur_enable_attitude``); ``sigma_att = sigma_dyn * QUAT_COEFF / 2``
-        weights the attitude as the reference does near the solution."""
+        weights the attitude as the reference does near the solution.  ``state_prior = (pose_idx [count], anchors [count,10],
+        infos [count,9,9])`` puts a Gaussian prior on the 9-DoF state ``[dp, dtheta, dv]`` of the chosen poses of a handle with the
+        dynamics factor (``vba_schur_enable_state_prior``); :func:`prior_for_first_pose` makes one from the
+        :meth:`handoff` of the window before."""
+        if state_prior is not None and time_idx is None:
+            raise ValueError("the state prior is only valid together with time_idx and sigma_dyn")
         if (time_idx is None) != (sigma_dyn is None):
             raise ValueError("time_idx and sigma_dyn switch on the dynamics factor together: give both or neither")
         if (cumrot is None) != (sigma_att is None):
@@ -164,6 +169,21 @@ class SchurBA:
                 if c.shape != (self.n, 4):
                     raise ValueError("cumrot needs one quaternion per pose")
                 self._check(self.lib.vba_schur_enable_attitude(self.h, c.ctypes.data_as(PD), float(sigma_att)))
+            except Exception:
+                self.close()
+                raise
+        self.prior_count = 0
+        if state_prior is not None:
+            try:
+                idx, anchors, infos = state_prior
+                idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+                an = np.ascontiguousarray(anchors, dtype=np.float64)
+                lam = np.ascontiguousarray(infos, dtype=np.float64)
+                if an.shape != (idx.size, 10) or lam.shape != (idx.size, 9, 9):
+                    raise ValueError("state_prior needs one anchor [10] and one information matrix [9, 9] per index")
+                self._check(self.lib.vba_schur_enable_state_prior(self.h, int(idx.size), idx.ctypes.data_as(ctypes.POINTER(c_int)),
+                                                                  an.ctypes.data_as(PD), lam.ctypes.data_as(PD)))
+                self.prior_count = int(idx.size)
             except Exception:
                 self.close()
                 raise
@@ -267,6 +287,39 @@ class SchurBA:
     def attitude_edge_cost(self):
         """``sigma_att |a|^2 [n-1]``: the edges' shares of the cost at the state the last iterate started from."""
         return self._dynamics_fetch(9, (self.n - 1,))
+
+    def prior_residual(self):
+        """``e [count,9]`` of the state priors at the state the last iterate started from (a handle with the state prior)."""
+        return self._dynamics_fetch(10, (self.prior_count, 9))
+
+    def prior_jacobian(self):
+        """``J [count,3,3] = d (2 s eps) / d theta`` of the state priors at the state the last iterate started from."""
+        return self._dynamics_fetch(11, (self.prior_count, 3, 3))
+
+    def prior_cost(self):
+        """``e^T Lambda e [count]``: the priors' shares of the cost at the state the last iterate started from."""
+        return self._dynamics_fetch(12, (self.prior_count,))
+
+    def handoff(self, steps, cumrot_gap, process_noise=None, lamda=0.0, strict=True):
+        """``vba_schur_handoff`` at the resident state of a handle with the dynamics factor (``include/vinsat_ba.h``): the marginal
+        of the last pose propagated over ``steps`` seconds -- ``cumrot_gap [4]`` the rotation accumulated over them, scalar last,
+        ``process_noise [3]`` variances per second of position, attitude and velocity -- into what the next window's prior takes.
+        Returns ``dict(anchor [10], info [9,9], status)``; ``status``: 0, ``1 +`` the row of a non-positive pivot of the covariance
+        query, or -1 if the propagated covariance is not positive definite.  ``strict``: a non-zero status raises ``VbaError``;
+        without it the arrays come back filled with NaN.  Nothing on the handle changes."""
+        c = np.ascontiguousarray(cumrot_gap, dtype=np.float64).reshape(4)
+        q = None if process_noise is None else np.ascontiguousarray(process_noise, dtype=np.float64).reshape(3)
+        anchor, info, status = np.empty(10), np.empty((9, 9)), c_int()
+        self._check(self.lib.vba_schur_handoff(self.h, float(lamda), int(steps), c.ctypes.data_as(PD), None if q is None else q.ctypes.data_as(PD),
+                                               anchor.ctypes.data_as(PD), info.ctypes.data_as(PD), byref(status)))
+        if status.value != 0 and strict:
+            if status.value < 0:
+                raise _lib.VbaError("schur handoff: the propagated covariance is not positive definite")
+            raise self._not_positive_definite("handoff", "reduced system", lamda, status.value)
+        return dict(anchor=anchor, info=info, status=status.value)
+
+    def last_handoff_ms(self):
+        return self._last_ms("vba_schur_last_handoff_ms")
 
     def cholesky_factor(self):
         """The factor of the last iterate, dense lower triangular: ``[6n, 6n]``, or ``[9n, 9n]`` over ``[pose | velocity]``
@@ -640,6 +693,12 @@ def scaled_power(power):
         out[key] = np.asarray(power[key]) * s0
     out["s0"] = s0
     return out
+
+
+def prior_for_first_pose(handoff):
+    """The ``state_prior`` tuple of :class:`SchurBA` for pose 0 of the next window from the dict of :meth:`SchurBA.handoff`."""
+    return (np.zeros(1, dtype=np.int32), np.asarray(handoff["anchor"], dtype=np.float64).reshape(1, 10),
+            np.asarray(handoff["info"], dtype=np.float64).reshape(1, 9, 9))
 
 
 def tile_bandwidth_of(structure, tile=64):
