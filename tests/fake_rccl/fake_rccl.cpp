@@ -5,6 +5,11 @@
 // the one GPU execute vba_sh_call with world = 2: slot order, +inf padding of unequal shards, rank-ordered reduce, id hand-over.
 // ncclAllGather here = wait for the stream, copy the send buffer to this rank's slot, barrier, copy every slot back, barrier.
 // Test infrastructure only (tests/test_sharded_fake_rccl_gpu.py builds it with g++); never shipped, never used by the product.
+//
+// The tap (fake_rccl_tap_*, below): opt-in and process-global.  While it is on, every ncclAllGather of this process appends a record
+// -- the element count, the bytes this rank sent, the bytes it received (all slots, rank order) -- to a list, taken from the host
+// copies the exchange is staged through anyway.  The list stops growing at kTapBytes and sets a flag instead.  Off (the default), the
+// all-gather does what it did before.  tests/test_gpu_sharded_carried.py reads the carried-keys protocol exchange by exchange from it.
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
@@ -18,6 +23,8 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
+
+#include <vector>
 
 namespace {
 
@@ -53,6 +60,20 @@ bool barrier(Shared* sh, int nranks) {          // sense-reversing, bounded: a r
     }
     return true;
 }
+
+constexpr size_t kTapBytes = 64u << 20;         // what the tap keeps at most (sent and received bytes of all records together)
+
+struct TapRecord {
+    long long count;                            // elements per rank
+    int elem, nranks;
+    std::vector<unsigned char> sent, recv;
+};
+
+struct Tap {
+    bool on = false, overflowed = false;
+    size_t bytes = 0;
+    std::vector<TapRecord> records;
+} g_tap;
 
 size_t type_size(ncclDataType_t t) {
     switch (t) {
@@ -120,6 +141,23 @@ ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcoun
     for (int r = 0; r < c->nranks; ++r)
         if (hipMemcpy(static_cast<char*>(recvbuff) + (size_t)r * bytes, c->sh->slots + (size_t)r * kSlotBytes, bytes, hipMemcpyHostToDevice) != hipSuccess)
             return ncclUnhandledCudaError;
+    if (g_tap.on) {                             // (before the second barrier: nobody overwrites a slot yet)
+        const size_t need = bytes * (size_t)(1 + c->nranks);
+        if (g_tap.overflowed || g_tap.bytes + need > kTapBytes) {
+            g_tap.overflowed = true;
+        } else {
+            TapRecord rec;
+            rec.count = (long long)sendcount;
+            rec.elem = (int)type_size(datatype);
+            rec.nranks = c->nranks;
+            const unsigned char* mine = c->sh->slots + (size_t)c->rank * kSlotBytes;
+            rec.sent.assign(mine, mine + bytes);
+            rec.recv.resize(bytes * (size_t)c->nranks);
+            for (int r = 0; r < c->nranks; ++r) std::memcpy(rec.recv.data() + (size_t)r * bytes, c->sh->slots + (size_t)r * kSlotBytes, bytes);
+            g_tap.bytes += need;
+            g_tap.records.push_back(std::move(rec));
+        }
+    }
     if (!barrier(c->sh, c->nranks)) return ncclSystemError;     // the slots may be overwritten again
     return ncclSuccess;
 }
@@ -131,6 +169,38 @@ ncclResult_t ncclCommDestroy(ncclComm_t comm) {
     if (c->rank == 0) shm_unlink(c->name);
     delete c;
     return ncclSuccess;
+}
+
+// ---- the tap.  fake_rccl_tap_enable(1) clears the list and starts recording, (0) stops and keeps the list.
+void fake_rccl_tap_enable(int on) {
+    if (on) {
+        g_tap.records.clear();
+        g_tap.bytes = 0;
+        g_tap.overflowed = false;
+    }
+    g_tap.on = on != 0;
+}
+
+int fake_rccl_tap_count(void) { return (int)g_tap.records.size(); }
+
+int fake_rccl_tap_overflowed(void) { return g_tap.overflowed ? 1 : 0; }
+
+// record i: element count, element size, ranks.  0, or -1 without such a record.
+int fake_rccl_tap_info(int i, long long* count, int* elem_bytes, int* nranks) {
+    if (i < 0 || (size_t)i >= g_tap.records.size() || !count || !elem_bytes || !nranks) return -1;
+    const TapRecord& r = g_tap.records[(size_t)i];
+    *count = r.count; *elem_bytes = r.elem; *nranks = r.nranks;
+    return 0;
+}
+
+// record i copied out: `sent` takes count * elem_bytes bytes, `recv` nranks times as many; `capacity_*` are the rooms in bytes.
+int fake_rccl_tap_copy(int i, void* sent, size_t capacity_sent, void* recv, size_t capacity_recv) {
+    if (i < 0 || (size_t)i >= g_tap.records.size() || !sent || !recv) return -1;
+    const TapRecord& r = g_tap.records[(size_t)i];
+    if (capacity_sent < r.sent.size() || capacity_recv < r.recv.size()) return -1;
+    std::memcpy(sent, r.sent.data(), r.sent.size());
+    std::memcpy(recv, r.recv.data(), r.recv.size());
+    return 0;
 }
 
 const char* ncclGetErrorString(ncclResult_t r) {

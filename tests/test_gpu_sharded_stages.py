@@ -69,8 +69,8 @@ exact: every one EQUAL.
   padded                             count            40     130 / 128  20     2.7000000143486886
   all-tied                           overflow-short   1024   128        511    2.6999999992722223
 
-Nothing comes near a bar.  Not covered here: the carried-keys protocol (``k_sh_front``, ``vba_sh_run_schedule``, ``vba_sh_call``), which
-needs the library-issued exchanges and more than one process.
+Nothing comes near a bar.  The carried-keys protocol (``k_sh_front``, ``vba_sh_run_schedule``, ``vba_sh_call``), which needs the
+library-issued exchanges and more than one process, is taken exchange by exchange in tests/test_gpu_sharded_carried.py.
 """
 import numpy as np
 import pytest
